@@ -8,11 +8,18 @@ GPU): one stream of N hours is sharded by STFT frames (sonar/shard.py) --
 rank g holds its frames' samples plus the 768-sample halo, generated on its
 own device by sample index -- with no data-path collective ("scaling":
 "weak", 1 h per GPU); the RCCL all-gather that reassembles the feature
-timeline runs once after the timed region and is reported separately.  Extra fields: DTW cells/sec (C3 size, float64, cost
-matrix in HBM), roofline of the dominant kernel, CPU baseline (the oracle,
-a float64 C restatement of the Go path, on a bounded sample).
+timeline runs once after the timed region and is reported separately.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps, the result line (with the headline kernel's roofline from the HIP events
+of those same steps).  --full adds every other leg to the line: the float64
+headline variant, the CPU baseline and parity (the oracle, a float64 C
+restatement of the Go path), C1, DTW cells/sec (C3 size, float64), PCM ingest,
+the batched entry, C5, C3, C4, the comparator and content-detector rows; the
+per-leg options below only matter with --full.  --dump-outputs DIR saves what
+the last timed step computed as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -90,7 +97,33 @@ def parse():
     ap.add_argument("--no-f64", action="store_true", help="skip the float64 headline variant")
     ap.add_argument("--dump-dir", default=None,
                     help="rank 0 saves the gathered MFCC timeline and C5 records there (tests of the N > 1 path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (f64 variant, CPU baselines and parity, C1, DTW, "
+                         "ingest, batch, C5, C3, C4, C6, C7); off: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save the last step's outputs as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, mfcc, world, rank, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path's last step handed its caller -- this rank's (F, 13)
+    float32 MFCC rows -- as DIR/mfcc.npy (one GPU) or DIR/mfcc_rank<g>.npy (N ranks, the budget split
+    evenly).  Rows over the budget are replaced by a seeded sample of whole rows in frame order,
+    whose indices go to DIR/<name>_rows.npy; the inputs are a function of the sample index
+    (sonar/shard.py), so two builds run with the same arguments are compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    a = mfcc.detach().cpu().numpy()
+    name = "mfcc" if world == 1 else f"mfcc_rank{rank}"
+    share = budget // world - 4096                                  # this rank's bytes, .npy headers aside
+    if a.nbytes > share:
+        max_rows = max(1, share // (a.shape[1] * a.itemsize + 8))   # a sampled row also costs its index
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max_rows, replace=False))
+        np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def dist_setup():
@@ -1148,6 +1181,8 @@ def main():
     elapsed = max_over_ranks(elapsed, world)
     ms_per_step = elapsed / args.steps * 1e3
     value = F_total / (elapsed / args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
 
     # RCCL all-gather of the MFCC timeline (reassembly of the frame-sharded stream
     # over xGMI), once, outside the timed region
@@ -1179,6 +1214,10 @@ def main():
             errors[f"{name}_error"] = f"{type(e).__name__}: {e}"
             traceback.print_exc(file=sys.stderr)
 
+    if not args.full:                   # a plain run is the headline alone: every leg below is off
+        args.no_f64 = args.no_cpu_baseline = True
+        args.c1 = args.dtw_len = args.ingest_reps = args.batch_signals = args.c5_pairs = 0
+        args.c3_seconds = args.c4_seconds = args.c6_gallery = args.c7_seconds = 0
     out64 = None
     if not args.no_f64:
         def f64_leg():
@@ -1235,6 +1274,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "warmup_extra_steps": warm_extra,
+        "full": bool(args.full),
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "weak",

@@ -26,6 +26,28 @@ def test_c5_roofline_bytes_and_families():
     assert {"dtw_band", "features"} <= set(shares)
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: an output within the budget is saved whole as float32; a larger one as a
+    seeded sample of whole rows in frame order with their indices, the two files within the budget."""
+    import numpy as np
+    import torch
+    x = torch.arange(13 * 1000, dtype=torch.float32).reshape(1000, 13)
+    bench.dump_outputs(str(tmp_path / "a"), x, 1, 0)
+    a = np.load(tmp_path / "a" / "mfcc.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["mfcc.npy"]
+    assert a.dtype == np.float32 and np.array_equal(a, x.numpy())
+    for d in ("b", "c"):                                   # the sample is the same from run to run
+        bench.dump_outputs(str(tmp_path / d), x, 1, 0, budget=20000)
+    b, rows = np.load(tmp_path / "b" / "mfcc.npy"), np.load(tmp_path / "b" / "mfcc_rows.npy")
+    assert b.dtype == np.float32 and rows.dtype == np.float64
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(b, x.numpy()[rows.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 20000
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "mfcc_rows.npy"))
+    bench.dump_outputs(str(tmp_path / "r"), x, 2, 1)       # N ranks: one file per rank
+    assert sorted(os.listdir(tmp_path / "r")) == ["mfcc_rank1.npy"]
+
+
 def test_committed_pmc_summaries_load():
     dtw = bench.load_pmc_bytes("*dtw_pmc*.json", "dtw_band_kernel<12, true, false, false")
     assert dtw is not None and dtw["bytes_per_launch"] > 0

@@ -49,7 +49,7 @@ def test_bench_two_ranks_equal_single_rank(ctx, tmp_path):
     env = dict(os.environ, SONAR_BENCH_ONE_DEVICE="1", SONAR_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--seconds", str(seconds), "--steps", "2", "--warmup", "1", "--dtw-len", "0",
+           "--full", "--gpus", "2", "--seconds", str(seconds), "--steps", "2", "--warmup", "1", "--dtw-len", "0",
            "--c5-pairs", str(npairs), "--c5-seconds", str(c5_seconds), "--c5-max-lag", "5", "--c5-workers", "8",
            "--reps", "1", "--no-cpu-baseline", "--no-f64", "--ingest-reps", "0", "--c3-seconds", "0",
            "--c4-seconds", "0", "--c6-gallery", "0", "--c7-seconds", "0", "--hw-queues", "16",
@@ -66,6 +66,7 @@ def test_bench_two_ranks_equal_single_rank(ctx, tmp_path):
     pcm = shard.stream_pcm(0, n, device="cuda")
     F = sonar.stft_frames(n, W, H)
     out = torch.empty((F, 13), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()        # pcm was written on torch's stream; ctx launches on its own non-blocking one
     ctx.fingerprint_device(pcm.data_ptr(), n, _mfcc_cfg(ctx), mfcc=out.data_ptr())
     torch.cuda.synchronize()
     assert ctx.last_fp_kernel() == "mfcc_pair_kernel"

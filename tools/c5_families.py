@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Group a rocprofv3 kernel-stats CSV of a C5 run (bench.py with only the C5 leg, or
+"""Group a rocprofv3 kernel-stats CSV of a C5 run (bench.py --full with only the C5 leg, or
 tools/c5_stress.py) into kernel families and write their GPU-time shares as JSON.
 
     python3 tools/c5_families.py <kernel_stats.csv> <out.json> [--note TEXT]

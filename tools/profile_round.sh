@@ -1,14 +1,14 @@
 #!/bin/bash
-# Round profile on the GPU box: kernel-trace stats of the default bench command,
+# Round profile on the GPU box: kernel-trace stats of the full bench command (bench.py --full),
 # separate FETCH_SIZE / WRITE_SIZE PMC passes (never combined with trace domains),
-# then the plain bench line.  Usage: bash tools/profile_round.sh <tag>
+# then the full bench line, untraced.  Usage: bash tools/profile_round.sh <tag>
 set -o pipefail
 TAG=${1:-r01}
 R="$GRAFT_REPO_ROOT"; [ -z "$R" ] && R=/root/repo
 OUT="$R/gpurun_out/prof_$TAG"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-    python3 "$R/bench.py" > "$OUT/bench_traced.log" 2>&1 || { echo "trace pass failed"; exit 1; }
+    python3 "$R/bench.py" --full > "$OUT/bench_traced.log" 2>&1 || { echo "trace pass failed"; exit 1; }
 rm -f "$OUT"/trace/*_kernel_trace.csv   # per-dispatch rows: tens of MB, the stats CSV is the summary
 echo "trace done"
 # the headline alone under the tracer, 200 timed steps after 20 warm-up steps: the stats average is
@@ -30,6 +30,6 @@ done
 # PMC and headline-trace runs skip the fp_batch leg, whose 1000 per-signal launches share the kernel's name
 (cd "$R" && python3 tools/traffic_summary.py "$OUT" "$TAG" mfcc_pair > "$OUT/traffic_summary.log") \
     || { echo "traffic summary failed"; exit 1; }
-timeout -k 10 600 python3 "$R/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; exit 1; }
+timeout -k 10 600 python3 "$R/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; exit 1; }
 cat "$OUT/bench.json"
 cp "$OUT/bench.json" "$R/profiles/${TAG}_bench.json"

@@ -1,6 +1,6 @@
 """Turn a tools/profile_round.sh output directory into the committed profiles/<tag>_*.
 
-profiles/<tag>_kernel_stats.csv : rocprofv3 --kernel-trace --stats summary of `python3 bench.py`
+profiles/<tag>_kernel_stats.csv : rocprofv3 --kernel-trace --stats summary of `python3 bench.py --full`
 profiles/<tag>_traffic.json     : per-launch HBM bytes of the fused kernel from FETCH_SIZE/WRITE_SIZE
 Units/corrections per MI355X_MICROARCH.md "HBM": counters are KiB; on gfx950 FETCH_SIZE
 reports half the bytes of wide coalesced streaming reads, so it is doubled."""
