@@ -24,6 +24,9 @@
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
  *   sonar_dtw                  <- DTWAlignment.Align (algorithms/stats/dtw.go:55)
+ *   sonar_dtw_params           <- NewDTWAlignmentWithParams(...).Align (dtw.go:45-52, 137-162; distance.go)
+ *   sonar_dtw_quality          <- DTWAlignment.GetAlignmentQuality (dtw.go:253-286)
+ *   sonar_dtw_optimize_step_pattern <- DTWAlignment.OptimizeStepPattern (dtw.go:288-311)
  *   sonar_formants             <- FormantAnalyzer.AnalyzeMultipleFrames / AnalyzeFormants
  *                                 (algorithms/speech/format.go:85-449) over LPCAnalyzer.Analyze
  *                                 (algorithms/speech/lpc.go:44-265)
@@ -289,13 +292,56 @@ int sonar_chroma_stft(sonar_ctx* ctx, const double* pcm, int64_t n, int64_t n_fr
 int sonar_ncc(sonar_ctx* ctx, const double* a, int64_t na, const double* b, int64_t nb,
               int32_t max_lag, double* corr, double* metrics, int32_t device_ptrs);
 
-/* ---- path B: DTW (float64, Euclidean, symmetric2, optional Sakoe-Chiba band)
+/* ---- path B: DTW (float64, optional Sakoe-Chiba band).  sonar_dtw is the default
+ * DTWAlignment (Euclidean, symmetric2); sonar_dtw_params takes NewDTWAlignmentWithParams'
+ * step pattern and metric (below).
  * q: nq x dim, r: nr x dim row-major.  path_* capacity >= nq + nr.  cost
  * (nullable) receives costMatrix[1:] = nq x (nr+1) (dtw.go:96).  Path points
  * are in forward order with cost = C[i][j] - C[i-1][j-1] (dtw.go:165-188). */
 int sonar_dtw(sonar_ctx* ctx, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim,
               int32_t band, double* distance, int32_t* path_q, int32_t* path_r, double* path_cost,
               int64_t* path_len, double* cost, int32_t device_ptrs);
+
+/* stats.NewDTWAlignmentWithParams(constraintBand, stepPattern, metric) (dtw.go:45-52).
+ * Step patterns, applyStepPattern (dtw.go:137-162): symmetric2 Min(Min(up, left), diag),
+ * asymmetric Min(up, left), symmetric1 Min(up+1, Min(left+1, diag)).  "asymmetric" never reads
+ * C[0][0], so with finite inputs every cell is +Inf: distance +Inf, a path of nq + nr points up
+ * column nr and along row 0 (query index -1), cost NaN where i > 0 and j > 0.
+ * Metrics, GetDistanceFunction (distance.go:10-26) in DistanceMetric's iota order
+ * (clustering.go:23-28): Euclidean (:29-36), Manhattan (:39-45), Cosine (:48-65; 1.0 when either
+ * norm is 0; may be slightly negative), Pearson (:73-107; 1.0 when either square sum is 0).
+ * Mahalanobis (:150-153) and every other value are Euclidean, as in Go.  Cosine and Pearson can
+ * be NaN for finite inputs (overflow to Inf / Inf). */
+#define SONAR_DTW_STEP_SYMMETRIC2 0
+#define SONAR_DTW_STEP_ASYMMETRIC 1
+#define SONAR_DTW_STEP_SYMMETRIC1 2
+#define SONAR_DTW_METRIC_EUCLIDEAN 0
+#define SONAR_DTW_METRIC_MANHATTAN 1
+#define SONAR_DTW_METRIC_COSINE 2
+#define SONAR_DTW_METRIC_PEARSON 3
+#define SONAR_DTW_METRIC_MAHALANOBIS 4
+/* DTWAlignment.Align (dtw.go:55-103) of a DTWAlignment built with those parameters: sonar_dtw's
+ * arguments and outputs plus step_pattern and metric.  An unknown step_pattern is
+ * SONAR_ERR_INVALID "failed to fill cost matrix: unknown step pattern: <value>" (dtw.go:76-78,
+ * 159-160), after the empty-sequence check.  Symmetric2 with Euclidean runs sonar_dtw's code.
+ * (ConstrainedAlign, dtw.go:236-251, is a stub that calls Align: use this entry.) */
+int sonar_dtw_params(sonar_ctx* ctx, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim,
+                     int32_t band, int32_t step_pattern, int32_t metric, double* distance, int32_t* path_q,
+                     int32_t* path_r, double* path_cost, int64_t* path_len, double* cost, int32_t device_ptrs);
+/* DTWAlignment.GetAlignmentQuality (dtw.go:253-286), host only (no context, no GPU): out4 =
+ * {path_efficiency, diagonal_ratio, average_cost, normalized_distance}; average_cost is summed in
+ * path order; one point gives diagonal_ratio 0/0 = NaN as in Go.  path_len <= 0 (Go: an empty
+ * map) is SONAR_ERR_EMPTY. */
+int sonar_dtw_quality(const int32_t* path_q, const int32_t* path_r, const double* path_cost, int64_t path_len,
+                      int64_t nq, int64_t nr, double distance, double* out4);
+/* DTWAlignment.OptimizeStepPattern (dtw.go:288-311): three Align calls in the order symmetric2,
+ * asymmetric, symmetric1; *best = the SONAR_DTW_STEP_* with the smallest Distance by strict <,
+ * starting from symmetric2.  distances3 (nullable) receives the three distances, NaN for a call
+ * that failed (Go skips it).  Returns SONAR_OK even when all three fail (*best = symmetric2), as
+ * Go returns "symmetric2", nil. */
+int sonar_dtw_optimize_step_pattern(sonar_ctx* ctx, const double* q, int64_t nq, const double* r, int64_t nr,
+                                    int32_t dim, int32_t band, int32_t metric, int32_t device_ptrs, int32_t* best,
+                                    double* distances3);
 
 /* ---- LPC formants: FormantAnalyzer.AnalyzeMultipleFrames (algorithms/speech/format.go:427-449)
  * over FormantAnalyzer.AnalyzeFormants (:85-124) + LPCAnalyzer.Analyze (lpc.go:44-82).

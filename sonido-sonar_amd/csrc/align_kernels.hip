@@ -8,7 +8,9 @@
 //       mul/add (__d*_rn), so correlations -- and therefore the peak lag -- are
 //       bit-identical to a sequential float64 evaluation.
 //  DTW  DTWAlignment.Align / fillCostMatrix / findPreviousStep / backtrack
-//       (algorithms/stats/dtw.go:55-217) with EuclideanDistanceFunc (distance.go:29-36).
+//       (algorithms/stats/dtw.go:55-217) with EuclideanDistanceFunc (distance.go:29-36);
+//       NewDTWAlignmentWithParams' step patterns (dtw.go:137-162) and Manhattan / Cosine / Pearson
+//       metrics (distance.go:39-107) as further instances of the same band kernel.
 //       dtw_band_kernel   : ONE persistent launch; 64-row bands pipelined through an sc1
 //                           edge hand-off, lane = row, DPP neighbours, distance inline
 //                           (see the DTW section below for the layout)
@@ -651,12 +653,64 @@ __device__ __forceinline__ void dtw_local_stall(int role, int32_t* sync, int* ct
   }
 }
 
-template <int D, bool FAST, bool BANDED, bool BATCH = false>
+// The local distance of the params family (METRIC >= 0), split so that the distance waves keep one
+// multiply-add (or |a - b|) chain per cell: dtw_term is the k-th term of the cell's sum, dtw_dist the
+// finish.  (a0, a1) / (b0, b1) are the two per-row scalars of the prepared query / reference row
+// (dtw_prepare_kernel): they are the same bits as Go's per-pair sums, whose terms do not depend on the
+// other row.  All unfused; /, sqrt and fabs are correctly rounded.
+template <int METRIC>
+__device__ __forceinline__ double dtw_term(double qk, double rk) {
+  if constexpr (METRIC == DTW_METRIC_MANHATTAN) return __builtin_fabs(qk - rk);   // distance.go:39-45
+  else if constexpr (METRIC >= DTW_METRIC_COSINE) return qk * rk;                 // :54, :93
+  else { const double df = qk - rk; return df * df; }                            // :29-36
+}
+template <int METRIC>
+__device__ __forceinline__ double dtw_dist(double sum, double a0, double a1, double b0, double b1) {
+  if constexpr (METRIC == DTW_METRIC_MANHATTAN) return sum;
+  else if constexpr (METRIC == DTW_METRIC_COSINE)                                 // distance.go:59-64
+    return (a0 == 0 || b0 == 0) ? 1.0 : 1.0 - sum / (a1 * b1);
+  else if constexpr (METRIC == DTW_METRIC_PEARSON)                                // distance.go:98-103
+    return (a0 == 0 || b0 == 0) ? 1.0 : 1.0 - __builtin_fabs(sum / sqrt(a0 * b0));
+  else return sqrt(sum);
+}
+// applyStepPattern (dtw.go:137-162) with math.Min's rules; `pattern` is block-uniform
+__device__ __forceinline__ double dtw_step_min(int pattern, double up, double left, double dg) {
+  if (pattern == DTW_STEP_ASYMMETRIC) return go_min(up, left);
+  if (pattern == DTW_STEP_SYMMETRIC1) return go_min(up + 1.0, go_min(left + 1.0, dg));
+  return go_min(go_min(up, left), dg);
+}
+
+// one cell's local distance for a runtime dimension, from global memory (rows of dim, or for Cosine
+// and Pearson dim + 2, doubles): the metric's sum in Go's order, then its finish
+template <int METRIC>
+__device__ __forceinline__ double dtw_cell_rt(const double* qa, const double* rb, int dim) {
+  double sum = 0.0;
+  for (int k = 0; k < dim; ++k) sum = sum + dtw_term<METRIC>(qa[k], rb[k]);
+  if constexpr (METRIC >= DTW_METRIC_COSINE)
+    return dtw_dist<METRIC>(sum, qa[dim], qa[dim + 1], rb[dim], rb[dim + 1]);
+  else
+    return dtw_dist<METRIC>(sum, 0.0, 0.0, 0.0, 0.0);
+}
+
+// The band kernel.  METRIC < 0 (the default): Euclidean / symmetric2, every instance as before.
+// METRIC >= 0, the params family (NewDTWAlignmentWithParams, dtw.go:45-52; D = 12 or 0, 2 x 4
+// instances): that metric in the distance waves and the step pattern of a.mode, a runtime value, in
+// the sweep; same rings, tickets and bounded waits.  FAST is false there (go_min and Go's strict-<
+// direction code: a Cosine or Pearson distance can be negative or, from finite inputs, NaN, and
+// "asymmetric" leaves every cell +Inf) and BANDED true (the host passes INT32_MAX for "no band":
+// exact, nq + nr <= INT32_MAX).  For Cosine and Pearson a.q / a.r are the prepared rows of dim + 2
+// doubles (dtw_prepare_kernel).
+template <int D, bool FAST, bool BANDED, bool BATCH = false, int METRIC = -1>
 // (2 blocks of 8 waves per CU: at least 4 waves per SIMD, <= 128 VGPRs)
 __global__ __launch_bounds__(64 * DTW_WAVES, BATCH ? DTW_BATCH_MINWAVES : DTW_MINWAVES)
 void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
-  constexpr int DR = D > 0 ? D : 1;
+  constexpr bool PARAMS = METRIC >= 0;
+  constexpr bool PREP = METRIC >= DTW_METRIC_COSINE;
+  static_assert(!PARAMS || (!FAST && BANDED && !BATCH), "the params family is exact, banded, single");
+  constexpr int GR = D + (PREP ? 2 : 0);             // doubles per row in global memory (D > 0)
+  constexpr int DR = D > 0 ? GR : 1;                 // ... held in registers and in the ring
   constexpr int DS = dtw_ring_stride<D>();
+  static_assert(DR <= DS, "a prepared row fits its ring slot");
   constexpr int FEEDER_WAVE = DTW_FEEDER_WAVE;
   constexpr int CODE_WAVE = DTW_CODE_WAVE;
   constexpr int EDGE_WAVE = DTW_EDGE_WAVE;
@@ -781,7 +835,7 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
     auto prefetch = [&](int64_t blk) {
       const int64_t row = DTW_RBLK * blk + lane;
 #pragma unroll
-      for (int k = 0; k < DR; ++k) pv[k] = (lane < DTW_RBLK && row < nr) ? DTW_GLOBAL(a.r)[row * D + k] : 0.0;
+      for (int k = 0; k < DR; ++k) pv[k] = (lane < DTW_RBLK && row < nr) ? DTW_GLOBAL(a.r)[row * GR + k] : 0.0;
     };
     if constexpr (D > 0) prefetch(0);
     while (true) {
@@ -970,13 +1024,19 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
   double qv[DR];
   if constexpr (D > 0) {
 #pragma unroll
-    for (int k = 0; k < D; ++k) qv[k] = DTW_GLOBAL(a.q)[qrow * D + k];
+    for (int k = 0; k < DR; ++k) qv[k] = DTW_GLOBAL(a.q)[qrow * GR + k];
   }
   // local distance of the lane's cell at step t for a runtime dimension (D == 0), from global
   // memory (EuclideanDistanceFunc order, unfused)
   auto dist_rt = [&](int64_t t) -> double {
     double sum = 0.0;
     const int64_t jj = t - lane + 1;
+    if constexpr (PARAMS) {
+      // the metric's sum in Go's order, then its finish (cells outside the matrix: never stored)
+      if (!(row_ok && jj >= 1 && jj <= nr)) return 0.0;
+      const int rl = dim + (PREP ? 2 : 0);
+      return dtw_cell_rt<PARAMS ? METRIC : 0>(a.q + qrow * rl, a.r + (jj - 1) * rl, dim);
+    }
     if (row_ok && jj >= 1 && jj <= nr) {
       const double* qa = a.q + qrow * dim;
       const double* rb = a.r + (jj - 1) * dim;
@@ -992,6 +1052,9 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
     // ---------------------------------------------------------- distance waves
     if (DTW_DIST_PRIO) __builtin_amdgcn_s_setprio(DTW_DIST_PRIO);
     const int w = dtw_dist_index(wave);
+    // cells interleaved per pass; 2 where every cell ends in a division (Cosine, Pearson): with 4
+    // or 8 of those in flight the wave spills the 128-register budget (scratch 64 / 416 B per lane)
+    constexpr int DG = PREP ? 2 : DTW_DG;
     for (int64_t c = w; DTW_ECH * c < S; c += DTW_NDW) {
       const int64_t t0 = DTW_ECH * c;
       // ring slots of steps t0..t0+7 were last read by the sweep for steps t0-DQ..t0-DQ+7
@@ -1007,16 +1070,39 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
         // the chains interleave.
         const double* rw0 = ring + (int)((t0 - lane) & (DTW_RROWS - 1)) * DS;
 #pragma unroll
-        for (int g0 = 0; g0 < DTW_ECH; g0 += DTW_DG) {   // DTW_DG interleaved chains at a time
-          double sum[DTW_DG];
-          if constexpr (D % 2 == 0) {
+        for (int g0 = 0; g0 < DTW_ECH; g0 += DG) {   // DG interleaved chains at a time
+          double sum[DG];
+          if constexpr (PARAMS) {
+            // every chain starts at Go's 0.0 (a product can be -0, and 0.0 + -0 is +0)
+#pragma unroll
+            for (int u = 0; u < DG; ++u) sum[u] = 0.0;
+          }
+          if constexpr (PARAMS && D % 2 == 0) {
 #pragma unroll
             for (int k = 0; k < D; k += 2) {
-              double2 rv[DTW_DG];
+              double2 rv[DG];
 #pragma unroll
-              for (int u = 0; u < DTW_DG; ++u) rv[u] = *reinterpret_cast<const double2*>(rw0 + (g0 + u) * DS + k);
+              for (int u = 0; u < DG; ++u) rv[u] = *reinterpret_cast<const double2*>(rw0 + (g0 + u) * DS + k);
 #pragma unroll
-              for (int u = 0; u < DTW_DG; ++u) {
+              for (int u = 0; u < DG; ++u) {
+                sum[u] = sum[u] + dtw_term<METRIC>(qv[k], rv[u].x);
+                sum[u] = sum[u] + dtw_term<METRIC>(qv[k + 1], rv[u].y);
+              }
+            }
+          } else if constexpr (PARAMS) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+#pragma unroll
+              for (int u = 0; u < DG; ++u) sum[u] = sum[u] + dtw_term<METRIC>(qv[k], rw0[(g0 + u) * DS + k]);
+            }
+          } else if constexpr (D % 2 == 0) {
+#pragma unroll
+            for (int k = 0; k < D; k += 2) {
+              double2 rv[DG];
+#pragma unroll
+              for (int u = 0; u < DG; ++u) rv[u] = *reinterpret_cast<const double2*>(rw0 + (g0 + u) * DS + k);
+#pragma unroll
+              for (int u = 0; u < DG; ++u) {
                 const double d0 = qv[k] - rv[u].x;
                 sum[u] = k == 0 ? d0 * d0 : sum[u] + d0 * d0;   // 0.0 + x == x for x >= +0 or NaN
                 const double d1 = qv[k + 1] - rv[u].y;
@@ -1027,28 +1113,38 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
 #pragma unroll
             for (int k = 0; k < D; ++k) {
 #pragma unroll
-              for (int u = 0; u < DTW_DG; ++u) {
+              for (int u = 0; u < DG; ++u) {
                 const double d0 = qv[k] - rw0[(g0 + u) * DS + k];
                 sum[u] = k == 0 ? d0 * d0 : sum[u] + d0 * d0;
               }
             }
           }
-          if constexpr (FAST) {
+          if constexpr (PREP) {
+            // the reference row's scalars sit after its D values in the ring slot (one 16-B read)
+#pragma unroll
+            for (int u = 0; u < DG; ++u) {
+              const double2 bs = *reinterpret_cast<const double2*>(rw0 + (g0 + u) * DS + D);
+              dv[g0 + u] = dtw_dist<METRIC>(sum[u], qv[D], qv[D + 1], bs.x, bs.y);
+            }
+          } else if constexpr (PARAMS) {
+#pragma unroll
+            for (int u = 0; u < DG; ++u) dv[g0 + u] = dtw_dist<METRIC>(sum[u], 0.0, 0.0, 0.0, 0.0);
+          } else if constexpr (FAST) {
             // finite inputs: sums are finite and >= 0; the short sqrt when every lane's DG sums
             // are in its range (all but exact or near-exact zero distances), else sqrt()
             double mn = sum[0];
 #pragma unroll
-            for (int u = 1; u < DTW_DG; ++u) mn = vmin_f64(mn, sum[u]);
+            for (int u = 1; u < DG; ++u) mn = vmin_f64(mn, sum[u]);
             if (__builtin_amdgcn_ballot_w64(!(mn >= DTW_SQRT_MIN)) == 0) {
 #pragma unroll
-              for (int u = 0; u < DTW_DG; ++u) dv[g0 + u] = sqrt_normal(sum[u]);
+              for (int u = 0; u < DG; ++u) dv[g0 + u] = sqrt_normal(sum[u]);
             } else {
 #pragma unroll
-              for (int u = 0; u < DTW_DG; ++u) dv[g0 + u] = sqrt(sum[u]);
+              for (int u = 0; u < DG; ++u) dv[g0 + u] = sqrt(sum[u]);
             }
           } else {
 #pragma unroll
-            for (int u = 0; u < DTW_DG; ++u) dv[g0 + u] = sqrt(sum[u]);
+            for (int u = 0; u < DG; ++u) dv[g0 + u] = sqrt(sum[u]);
           }
         }
       } else {
@@ -1076,6 +1172,7 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
   double out = inf;                                   // C[i][j-1]; C[i][0] = +Inf
   double up_prev = (lane == 0 && b == 0) ? 0.0 : inf; // C[i-1][j-1]; C[0][0] = 0
   const int64_t band = a.band;
+  const int pattern = a.mode & 0xFF;                  // PARAMS only: the step pattern (block-uniform)
 
   // chunk of steps [s0, s0+8) may start once its distances, its top-edge columns (through s0+8)
   // and the code wave's progress (C-ring slots reused after DTW_OQ steps) are there.  32-bit
@@ -1170,7 +1267,8 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
     const double up = shr1(out, l0up);               // C[i-1][j]; lane 0 takes l0up
     const double left = out, dg = up_prev;
     double best;
-    if constexpr (FAST) best = vmin_f64(up, vmin_f64(left, dg));   // all >= +0 or +Inf: order-free
+    if constexpr (PARAMS) best = dtw_step_min(pattern, up, left, dg);
+    else if constexpr (FAST) best = vmin_f64(up, vmin_f64(left, dg));   // all >= +0 or +Inf: order-free
     else best = go_min(go_min(up, left), dg);                      // math.Min: NaN / -Inf / -0 rules
     double v = d + best;
     const int64_t j = s - lane + 1;
@@ -1735,8 +1833,11 @@ __global__ __launch_bounds__(256) void dtw_path_runs_kernel(DtwArgs a_in, const 
   }
 }
 
-template <bool BATCH, int D>
-__global__ __launch_bounds__(64) void dtw_path_tile_kernel(DtwArgs a_in, const DtwArgs* args) {
+// PARAMS (dtw_path_tile_params_kernel, D == 0): the metric and step pattern of a.mode, as the
+// band kernel's params family computed them (q and r are the rows that family read)
+template <bool BATCH, int D, bool PARAMS>
+__device__ __forceinline__ void dtw_path_tile_body(DtwArgs a_in, const DtwArgs* args) {
+  static_assert(!PARAMS || (D == 0 && !BATCH), "the params tile pass: runtime dimension, single");
   // Registers only for the recurrence (the band kernel's sweep shape: lane = row, at step st lane l
   // relaxes column c = st - l, C[i-1][j] by DPP from lane l-1, C[i-1][j-1] one step later, C[i][j-1]
   // its own), so the block needs ~7 KB of LDS and co-resides with the band kernel's blocks (the
@@ -1763,7 +1864,10 @@ __global__ __launch_bounds__(64) void dtw_path_tile_kernel(DtwArgs a_in, const D
   const double leftc = bj == 0 ? inf : a.CK[(((int64_t)bi * (nr >> 6) + bj - 1) << 6) + lane];   // C[i][jb]
   rlo[lane] = 64; rhi[lane] = -1; rf[lane] = INT32_MAX;
   const int dim = a.dim;
-  const double* qrow = a.q + (i <= nq ? i - 1 : 0) * dim;
+  const int pattern = a.mode & 0xFF, metric = a.mode >> 8;
+  // doubles per row: PARAMS with Cosine or Pearson reads the prepared rows
+  const int rl = PARAMS && metric >= DTW_METRIC_COSINE ? dim + 2 : dim;
+  const double* qrow = a.q + (i <= nq ? i - 1 : 0) * rl;
   double qv[D > 0 ? D : 1];
   if constexpr (D > 0) {
 #pragma unroll
@@ -1797,21 +1901,32 @@ __global__ __launch_bounds__(64) void dtw_path_tile_kernel(DtwArgs a_in, const D
     if (c >= 0 && c < 64) {
       const int64_t j = jb + 1 + c;
       const double left = v;
-      double sum = 0.0;
-      if constexpr (D > 0) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          const double df = qv[k] - Rt[c * D + k];
-          sum = sum + df * df;
-        }
+      double nv;
+      if constexpr (PARAMS) {
+        const double* rrow = a.r + (j <= nr ? j - 1 : 0) * rl;
+        double d;
+        if (metric == DTW_METRIC_MANHATTAN) d = dtw_cell_rt<DTW_METRIC_MANHATTAN>(qrow, rrow, dim);
+        else if (metric == DTW_METRIC_COSINE) d = dtw_cell_rt<DTW_METRIC_COSINE>(qrow, rrow, dim);
+        else if (metric == DTW_METRIC_PEARSON) d = dtw_cell_rt<DTW_METRIC_PEARSON>(qrow, rrow, dim);
+        else d = dtw_cell_rt<DTW_METRIC_EUCLIDEAN>(qrow, rrow, dim);
+        nv = d + dtw_step_min(pattern, up, left, dg);
       } else {
-        const double* rrow = a.r + (j <= nr ? j - 1 : 0) * dim;
-        for (int k = 0; k < dim; ++k) {
-          const double df = qrow[k] - rrow[k];
-          sum = sum + df * df;
+        double sum = 0.0;
+        if constexpr (D > 0) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) {
+            const double df = qv[k] - Rt[c * D + k];
+            sum = sum + df * df;
+          }
+        } else {
+          const double* rrow = a.r + (j <= nr ? j - 1 : 0) * dim;
+          for (int k = 0; k < dim; ++k) {
+            const double df = qrow[k] - rrow[k];
+            sum = sum + df * df;
+          }
         }
+        nv = sqrt(sum) + go_min(go_min(up, left), dg);
       }
-      double nv = sqrt(sum) + go_min(go_min(up, left), dg);
       if (a.band > 0 && (i - j > a.band || j - i > a.band)) nv = inf;   // outside the Sakoe-Chiba band
       v = nv;
       if (c >= mlo && c <= mhi) {
@@ -1820,6 +1935,41 @@ __global__ __launch_bounds__(64) void dtw_path_tile_kernel(DtwArgs a_in, const D
         if (i == nq && j == nr) *a.cnm = nv;
       }
     }
+  }
+}
+
+template <bool BATCH, int D>
+__global__ __launch_bounds__(64) void dtw_path_tile_kernel(DtwArgs a_in, const DtwArgs* args) {
+  dtw_path_tile_body<BATCH, D, false>(a_in, args);
+}
+__global__ __launch_bounds__(64) void dtw_path_tile_params_kernel(DtwArgs a_in, const DtwArgs* args) {
+  dtw_path_tile_body<false, 0, true>(a_in, args);
+}
+
+// Row preparation for Cosine and Pearson, once per call: thread per row, out[row] = the row's dim
+// values (Pearson: a[k] - meanA, distance.go:82-91), then the two scalars of dtw_dist -- Cosine
+// {normA, sqrt(normA)} (:55, :63), Pearson {sumSqA, 0} (:95).  Sequential sums in index order.
+__global__ __launch_bounds__(256) void dtw_prepare_kernel(const double* x, int64_t n, int dim, int metric, double* out) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const double* a = x + row * dim;
+  double* o = out + row * (dim + 2);
+  double s = 0.0;
+  if (metric == DTW_METRIC_COSINE) {
+    for (int k = 0; k < dim; ++k) { o[k] = a[k]; s = s + a[k] * a[k]; }
+    o[dim] = s;
+    o[dim + 1] = sqrt(s);
+  } else {
+    double mean = 0.0;
+    for (int k = 0; k < dim; ++k) mean = mean + a[k];
+    mean = mean / (double)dim;
+    for (int k = 0; k < dim; ++k) {
+      const double df = a[k] - mean;
+      o[k] = df;
+      s = s + df * df;
+    }
+    o[dim] = s;
+    o[dim + 1] = 0.0;
   }
 }
 
@@ -1914,7 +2064,7 @@ int64_t dtw_cn_index(const DtwGeom& g, int64_t i, int64_t j) {
 
 int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, const DtwGeom& g, double* Cn,
                uint32_t* Dn, uint64_t* E, int32_t* sync_words, uint32_t* codes, int64_t* plen, uint64_t* trace,
-               hipStream_t s, hipEvent_t mid, double* CK) {
+               hipStream_t s, hipEvent_t mid, double* CK, int mode) {
   // sync_words: [0] ticket, [1] error bits, [2] non-finite flag (set by the caller's probe), [3]
   // unused, then the DTW_DIAG_WORDS-word diagnostic record at byte 16 (DTW_SYNC_BYTES in all)
   if (hipMemsetAsync(sync_words, 0, 2 * sizeof(int32_t), s) != hipSuccess) return -5;
@@ -1925,6 +2075,7 @@ int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, c
   a.CK = CK;
   a.diag = reinterpret_cast<uint64_t*>(sync_words + 4);
   a.dbg_stall = dtw_dbg_stall_band(false);
+  a.mode = mode;
   if (!Cn && !CK) return -1;
   const DtwBatch nob{};
   const dim3 grid((unsigned)g.nb), block(64 * DTW_WAVES);
@@ -1938,9 +2089,31 @@ int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, c
       else hipLaunchKernelGGL((dtw_band_kernel<DD, false, false>), grid, block, 0, s, a, nob);        \
     }                                                                                                 \
   } while (0)
-  if (dim == 12) SONAR_DTW_LAUNCH(12);
+#define SONAR_DTW_LAUNCH_PARAMS(DD)                                                                        \
+  do {                                                                                                     \
+    switch (mode >> 8) {                                                                                   \
+      case DTW_METRIC_MANHATTAN:                                                                           \
+        hipLaunchKernelGGL((dtw_band_kernel<DD, false, true, false, DTW_METRIC_MANHATTAN>), grid, block, 0, s, a, nob); \
+        break;                                                                                             \
+      case DTW_METRIC_COSINE:                                                                              \
+        hipLaunchKernelGGL((dtw_band_kernel<DD, false, true, false, DTW_METRIC_COSINE>), grid, block, 0, s, a, nob);    \
+        break;                                                                                             \
+      case DTW_METRIC_PEARSON:                                                                             \
+        hipLaunchKernelGGL((dtw_band_kernel<DD, false, true, false, DTW_METRIC_PEARSON>), grid, block, 0, s, a, nob);   \
+        break;                                                                                             \
+      default:                                                                                             \
+        hipLaunchKernelGGL((dtw_band_kernel<DD, false, true, false, DTW_METRIC_EUCLIDEAN>), grid, block, 0, s, a, nob); \
+    }                                                                                                      \
+  } while (0)
+  if (mode != 0) {
+    // the params family is always BANDED: no band = a band no |i - j| reaches (nq + nr <= INT32_MAX)
+    if (band <= 0) a.band = INT32_MAX;
+    if (dim == 12) SONAR_DTW_LAUNCH_PARAMS(12);
+    else SONAR_DTW_LAUNCH_PARAMS(0);
+  } else if (dim == 12) SONAR_DTW_LAUNCH(12);
   else if (dim == 1) SONAR_DTW_LAUNCH(1);
   else SONAR_DTW_LAUNCH(0);
+#undef SONAR_DTW_LAUNCH_PARAMS
 #undef SONAR_DTW_LAUNCH
   if (mid) hipEventRecord(mid, s);
   if (dtw_serial_walk()) {
@@ -1956,6 +2129,12 @@ int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, c
     hipLaunchKernelGGL(dtw_walk_scan_kernel<false>, dim3(1), dim3(1024), 0, s, a, none);
     hipLaunchKernelGGL((dtw_walk_band_kernel<true, false>), dim3((unsigned)g.nb), dim3(64), 0, s, a, none);
   }
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_dtw_prepare(const double* x, int64_t n, int dim, int metric, double* out, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(dtw_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, dim, metric, out);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -1976,7 +2155,10 @@ int launch_dtw_path_tiles(const DtwArgs& a, int64_t P, hipStream_t s) {
   if (hipMemsetAsync(a.runs, 0, 4, s) != hipSuccess) return -5;
   hipLaunchKernelGGL(dtw_path_runs_kernel<false>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, a,
                      (const DtwArgs*)nullptr);
-  if (a.dim == 12)
+  if (a.mode != 0)
+    hipLaunchKernelGGL(dtw_path_tile_params_kernel, dim3((unsigned)(dtw_run_words(g) - 2)), dim3(64), 0, s, a,
+                       (const DtwArgs*)nullptr);
+  else if (a.dim == 12)
     hipLaunchKernelGGL((dtw_path_tile_kernel<false, 12>), dim3((unsigned)(dtw_run_words(g) - 2)), dim3(64), 0, s, a,
                        (const DtwArgs*)nullptr);
   else

@@ -149,7 +149,8 @@ int ncc_enqueue(sonar_ctx* c, const double* da, int64_t na, const double* db, in
 void ncc_metrics_host(const double* corr, int64_t L, int64_t na, int64_t nb, double* metrics);
 // the path-tile pass's arguments (launch_dtw_path_tiles) of one DTW in checkpoint mode
 sonar::DtwArgs tile_args(const double* q, const double* r, int dim, int band, const sonar::DtwGeom& g, uint64_t* E,
-                         double* CK, int32_t* runs, int32_t* pq, int32_t* pr, double* pc, int64_t* plen, double* cnm);
+                         double* CK, int32_t* runs, int32_t* pq, int32_t* pr, double* pc, int64_t* plen, double* cnm,
+                         int mode = 0 /* dtw_mode: step pattern and metric */);
 // the band kernel's status block of one DTW (int32 sync[4] + the DtwArgs::diag record): adds its
 // counters to c->dtw_ctr and, when the DTW timed out, returns the failure text with the record
 std::string dtw_status(sonar_ctx* c, const void* sync_block);

@@ -226,13 +226,26 @@ size_t dtw_dn_bytes(const DtwGeom& g);
 size_t dtw_edge_bytes(const DtwGeom& g);
 // offset (elements) of C[i][j] (1-based, i,j >= 1) inside Cn
 int64_t dtw_cn_index(const DtwGeom& g, int64_t i, int64_t j);
-// forward sweep + backtrack; `fast` = every input finite (no NaN path in math.Min)
+// applyStepPattern's patterns (dtw.go:137-162) and GetDistanceFunction's metrics (distance.go:10-26;
+// Mahalanobis and unknown values are Euclidean there and never reach the kernels)
+enum DtwStep : int { DTW_STEP_SYMMETRIC2 = 0, DTW_STEP_ASYMMETRIC = 1, DTW_STEP_SYMMETRIC1 = 2 };
+enum DtwMetric : int { DTW_METRIC_EUCLIDEAN = 0, DTW_METRIC_MANHATTAN = 1, DTW_METRIC_COSINE = 2,
+                       DTW_METRIC_PEARSON = 3 };
+inline int dtw_mode(int step, int metric) { return step | (metric << 8); }
+// Cosine and Pearson run on prepared rows of dim + 2 doubles (launch_dtw_prepare): the row's dim
+// values (Pearson: centred on its mean), then {normA, sqrt(normA)} (Cosine) or {sumSq, 0} (Pearson)
+inline int dtw_row_len(int dim, int metric) { return metric >= DTW_METRIC_COSINE ? dim + 2 : dim; }
+// out[n][dim + 2] from x[n][dim]; every sum in Go's index order, unfused (distance.go:49-58, 82-102)
+int launch_dtw_prepare(const double* x, int64_t n, int dim, int metric, double* out, hipStream_t s);
+// forward sweep + backtrack; `fast` = every input finite (no NaN path in math.Min).  mode 0 runs the
+// Euclidean / symmetric2 instances; any other mode (dtw_mode) the band kernel's params family, with
+// q and r the prepared rows (dtw_row_len doubles each) for Cosine and Pearson
 int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, const DtwGeom& g, double* Cn,
                uint32_t* Dn, uint64_t* E, int32_t* sync_words /* [0] ticket, [1] error */,
                uint32_t* codes /* walk moves, 2 bits each */, int64_t* plen,
                uint64_t* trace /* nullable, [nb][8] diagnostics */, hipStream_t s,
                hipEvent_t mid = nullptr /* recorded between the sweep and the walk */,
-               double* CK = nullptr /* Cn null: dtw_ck_bytes of checkpoint columns instead */);
+               double* CK = nullptr /* Cn null: dtw_ck_bytes of checkpoint columns instead */, int mode = 0);
 // wstart: scratch of (P + 15) / 16 int2 (each code word's starting cell).  Cn null: only the
 // points (and the zero cost of border points) are written; launch_dtw_path_tiles adds the costs
 int launch_dtw_path_cost(const double* Cn, const DtwGeom& g, const uint32_t* codes, int64_t P, int2* wstart,
@@ -283,7 +296,9 @@ struct DtwArgs {
   // without publishing more, so the
   // pipeline's bounded waits and its diagnostic record can be exercised; -1: off
   int32_t dbg_stall = -1;
-  int32_t pad_;
+  // step pattern | metric << 8 (dtw_mode); 0 = symmetric2 / Euclidean, the only mode of the batched
+  // launches.  Read by the band kernel's params family and the path-tile pass.
+  int32_t mode = 0;
 };
 constexpr int DTW_DIAG_WORDS = 16;
 // bytes of a single DTW's sync block (launch_dtw): 4 status words + the diagnostic record
@@ -297,7 +312,7 @@ int64_t dtw_run_words(const DtwGeom& g);
 // path costs and C[nq][nr] from CK + E (the band kernel's checkpoint columns and band edges), for
 // a path whose points (pq, pr) are already written: one wave per 64 x 64 tile the path visits
 // recomputes the tile's cells in the band kernel's arithmetic (bit-identical).  Needs a.q, r, dim,
-// band, nq, nr, nb, E, CK, pq, pr, pc, runs, cnm.
+// band, nq, nr, nb, E, CK, pq, pr, pc, runs, cnm, mode (q and r as launch_dtw took them).
 int launch_dtw_path_tiles(const DtwArgs& a, int64_t P, hipStream_t s);
 // n DTWs of 12-dim finite sequences, unbanded (the chroma DTWs of sonar_align_pairs), from a
 // device array of DtwArgs: the band kernel over all of them (block tickets run through DTW k's

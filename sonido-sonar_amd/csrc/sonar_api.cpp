@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -1160,11 +1161,19 @@ int sonar_ncc(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_
 }
 
 // ================================================================ DTW ====
-int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim, int32_t band,
-              double* distance, int32_t* path_q, int32_t* path_r, double* path_cost, int64_t* path_len, double* cost,
-              int32_t device_ptrs) {
+// DTWAlignment.Align (dtw.go:55-103) for one step pattern and metric (both already validated; mode 0
+// = symmetric2 / Euclidean is sonar_dtw, unchanged)
+static int dtw_run(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim, int32_t band,
+                   double* distance, int32_t* path_q, int32_t* path_r, double* path_cost, int64_t* path_len,
+                   double* cost, int32_t device_ptrs, int step, int metric) {
   if (!c) return SONAR_ERR_INVALID;
   if (nq <= 0 || nr <= 0 || !q || !r) return fail(c, SONAR_ERR_EMPTY, "empty sequences provided");
+  if (step < sonar::DTW_STEP_SYMMETRIC2 || step > sonar::DTW_STEP_SYMMETRIC1) {
+    // applyStepPattern's default case at the first filled cell (dtw.go:159-160), wrapped by Align (:76-78)
+    return fail(c, SONAR_ERR_INVALID,
+                "failed to fill cost matrix: unknown step pattern: " + std::to_string(step));
+  }
+  const int mode = sonar::dtw_mode(step, metric);
   if (dim <= 0) return fail(c, SONAR_ERR_INVALID, "feature dimension must be positive");
   if (nq + nr > (int64_t)INT32_MAX) return fail(c, SONAR_ERR_UNSUPPORTED, "sequence too long");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1177,6 +1186,16 @@ int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_
     HIP_TRY(c, hipMemcpyAsync(pq, q, nq * dim * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(pr, r, nr * dim * 8, hipMemcpyHostToDevice, s));
     dq = pq; dr = pr;
+  }
+  if (metric >= sonar::DTW_METRIC_COSINE) {
+    // Cosine / Pearson: the band kernel and the tile pass read prepared rows (launch_dtw_prepare)
+    const int rl = sonar::dtw_row_len(dim, metric);
+    double* qp = (double*)dbuf(c, "dtw.qp", (size_t)nq * rl * 8);
+    double* rp = (double*)dbuf(c, "dtw.rp", (size_t)nr * rl * 8);
+    if (!qp || !rp) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+    if (sonar::launch_dtw_prepare(dq, nq, dim, metric, qp, s) || sonar::launch_dtw_prepare(dr, nr, dim, metric, rp, s))
+      return fail(c, SONAR_ERR_DEVICE, "dtw launch failed");
+    dq = qp; dr = rp;
   }
   const sonar::DtwGeom g = sonar::dtw_geom(nq, nr);
   // the full cost store only when the caller asks for the cost matrix; otherwise every 64th
@@ -1195,11 +1214,12 @@ int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_
   if ((full ? !Cn : (!CK || !runs)) || !cnm_d || !Dn || !E || !sync || !codes || !pl)
     return fail(c, SONAR_ERR_NOMEM, "device allocation failed (cost matrix)");
   // math.Min's NaN / -Inf / -0 rules only matter when an input is not finite
-  bool fast = true;
-  if (!device_ptrs) {
+  // (the params family has no FAST instances: mode != 0 always runs the exact min)
+  bool fast = mode == 0;
+  if (fast && !device_ptrs) {
     for (int64_t k = 0; k < nq * dim && fast; ++k) fast = std::isfinite(q[k]);
     for (int64_t k = 0; k < nr * dim && fast; ++k) fast = std::isfinite(r[k]);
-  } else {
+  } else if (fast) {
     HIP_TRY(c, hipMemsetAsync(sync + 2, 0, 4, s));
     if (sonar::launch_nonfinite(dq, nq * dim, sync + 2, s) || sonar::launch_nonfinite(dr, nr * dim, sync + 2, s))
       return fail(c, SONAR_ERR_DEVICE, "dtw launch failed");
@@ -1215,7 +1235,7 @@ int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_
     if (!e) HIP_TRY(c, hipEventCreate(&e));
   hipEvent_t tend = timed_begin(c, s);
   HIP_TRY(c, hipEventRecord(c->dtw_ev[0], s));
-  if (sonar::launch_dtw(dq, dr, dim, band, fast, g, Cn, Dn, E, sync, codes, pl, trace, s, c->dtw_ev[1], CK) != 0)
+  if (sonar::launch_dtw(dq, dr, dim, band, fast, g, Cn, Dn, E, sync, codes, pl, trace, s, c->dtw_ev[1], CK, mode) != 0)
     return fail(c, SONAR_ERR_DEVICE, "dtw launch failed");
   HIP_TRY(c, hipEventRecord(c->dtw_ev[2], s));
   timed_end(c, s, tend);
@@ -1234,18 +1254,20 @@ int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_
     const std::string why = sonar::detail::dtw_status(c, sblk);
     if (!why.empty()) return fail(c, SONAR_ERR_DEVICE, why);
   }
-  int32_t* oq = path_q; int32_t* orr = path_r; double* oc = path_cost;
-  if (!device_ptrs) {
-    oq = (int32_t*)dbuf(c, "dtw.pq", cap * 4);
-    orr = (int32_t*)dbuf(c, "dtw.pr", cap * 4);
-    oc = (double*)dbuf(c, "dtw.pc", cap * 8);
-    if (!oq || !orr || !oc) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (path)");
-  }
+  // the path kernels always write all three arrays: the caller's device buffers, or scratch for host
+  // pointers and for any the caller left null (sonar_dtw_optimize_step_pattern wants distances only)
+  int32_t* oq = device_ptrs ? path_q : nullptr;
+  int32_t* orr = device_ptrs ? path_r : nullptr;
+  double* oc = device_ptrs ? path_cost : nullptr;
+  if (!oq) oq = (int32_t*)dbuf(c, "dtw.pq", cap * 4);
+  if (!orr) orr = (int32_t*)dbuf(c, "dtw.pr", cap * 4);
+  if (!oc) oc = (double*)dbuf(c, "dtw.pc", cap * 8);
+  if (!oq || !orr || !oc) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (path)");
   int2* wstart = (int2*)dbuf(c, "dtw.wstart", (size_t)((P + 15) / 16 + 1) * sizeof(int2));
   if (!wstart) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (path)");
   if (sonar::launch_dtw_path_cost(Cn, g, codes, P, wstart, oq, orr, oc, s) != 0 ||
       (!full && sonar::launch_dtw_path_tiles(sonar::detail::tile_args(dq, dr, dim, band, g, E, CK, runs, oq, orr, oc,
-                                                                        pl, cnm_d), P, s) != 0))
+                                                                        pl, cnm_d, mode), P, s) != 0))
     return fail(c, SONAR_ERR_DEVICE, "dtw path launch failed");
   HIP_TRY(c, hipEventRecord(c->dtw_ev[3], s));
   double cNM = 0;
@@ -1271,6 +1293,68 @@ int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_
   }
   if (path_len) *path_len = P;
   if (distance) *distance = cNM / (double)P;                      // dtw.go:88-91
+  return SONAR_OK;
+}
+
+int sonar_dtw(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim, int32_t band,
+              double* distance, int32_t* path_q, int32_t* path_r, double* path_cost, int64_t* path_len, double* cost,
+              int32_t device_ptrs) {
+  return dtw_run(c, q, nq, r, nr, dim, band, distance, path_q, path_r, path_cost, path_len, cost, device_ptrs,
+                 sonar::DTW_STEP_SYMMETRIC2, sonar::DTW_METRIC_EUCLIDEAN);
+}
+
+// GetDistanceFunction (distance.go:10-26): Mahalanobis and every unknown value are Euclidean
+static int dtw_metric(int32_t metric) {
+  return metric >= SONAR_DTW_METRIC_EUCLIDEAN && metric <= SONAR_DTW_METRIC_PEARSON ? metric
+                                                                                   : sonar::DTW_METRIC_EUCLIDEAN;
+}
+
+int sonar_dtw_params(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim,
+                     int32_t band, int32_t step_pattern, int32_t metric, double* distance, int32_t* path_q,
+                     int32_t* path_r, double* path_cost, int64_t* path_len, double* cost, int32_t device_ptrs) {
+  return dtw_run(c, q, nq, r, nr, dim, band, distance, path_q, path_r, path_cost, path_len, cost, device_ptrs,
+                 step_pattern, dtw_metric(metric));
+}
+
+int sonar_dtw_quality(const int32_t* path_q, const int32_t* path_r, const double* path_cost, int64_t path_len,
+                      int64_t nq, int64_t nr, double distance, double* out4) {
+  if (path_len <= 0) return SONAR_ERR_EMPTY;                      // dtw.go:254-256 (an empty map there)
+  if (!path_q || !path_r || !path_cost || !out4) return SONAR_ERR_INVALID;
+  const double P = (double)path_len;
+  out4[0] = (double)std::max(nq, nr) / P;                         // :261-262
+  int64_t diag = 0;
+  for (int64_t k = 1; k < path_len; ++k)                          // :265-271
+    if (path_q[k] > path_q[k - 1] && path_r[k] > path_r[k - 1]) ++diag;
+  out4[1] = (double)diag / (double)(path_len - 1);                // :272 (one point: 0 / 0)
+  double total = 0.0;
+  for (int64_t k = 0; k < path_len; ++k) total += path_cost[k];   // :275-278, in path order
+  out4[2] = total / P;                                            // :279
+  out4[3] = distance;                                             // :282
+  return SONAR_OK;
+}
+
+int sonar_dtw_optimize_step_pattern(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_t nr,
+                                    int32_t dim, int32_t band, int32_t metric, int32_t device_ptrs, int32_t* best,
+                                    double* distances3) {
+  if (!c) return SONAR_ERR_INVALID;
+  if (!best) return fail(c, SONAR_ERR_INVALID, "best must not be null");
+  // dtw.go:290-307: symmetric2, asymmetric, symmetric1; a failing Align is skipped; strict <
+  const int patterns[3] = {SONAR_DTW_STEP_SYMMETRIC2, SONAR_DTW_STEP_ASYMMETRIC, SONAR_DTW_STEP_SYMMETRIC1};
+  int32_t best_pattern = patterns[0];
+  double best_distance = std::numeric_limits<double>::infinity();
+  for (int k = 0; k < 3; ++k) {
+    double d = 0.0;
+    int64_t plen = 0;
+    const int rc = dtw_run(c, q, nq, r, nr, dim, band, &d, nullptr, nullptr, nullptr, &plen, nullptr, device_ptrs,
+                           patterns[k], dtw_metric(metric));
+    if (distances3) distances3[k] = rc == SONAR_OK ? d : std::numeric_limits<double>::quiet_NaN();
+    if (rc != SONAR_OK) continue;
+    if (d < best_distance) {
+      best_distance = d;
+      best_pattern = patterns[k];
+    }
+  }
+  *best = best_pattern;
   return SONAR_OK;
 }
 
@@ -1319,8 +1403,10 @@ std::string dtw_status(sonar_ctx* c, const void* sync_block) {
 }
 
 sonar::DtwArgs tile_args(const double* q, const double* r, int dim, int band, const sonar::DtwGeom& g, uint64_t* E,
-                         double* CK, int32_t* runs, int32_t* pq, int32_t* pr, double* pc, int64_t* plen, double* cnm) {
+                         double* CK, int32_t* runs, int32_t* pq, int32_t* pr, double* pc, int64_t* plen, double* cnm,
+                         int mode) {
   sonar::DtwArgs a{};
+  a.mode = mode;
   a.q = q; a.r = r; a.dim = dim; a.band = band;
   a.nq = g.nq; a.nr = g.nr; a.nb = g.nb; a.S = g.S; a.SW = g.SW;
   a.E = E; a.CK = CK; a.runs = runs; a.pq = pq; a.pr = pr; a.pc = pc; a.plen = plen; a.cnm = cnm;

@@ -603,6 +603,102 @@ func (x *Context) DTW(q, r [][]float64, band int, wantCost bool) (*DTWResult, er
 	return res, nil
 }
 
+// DistanceMetric mirrors stats.DistanceMetric (clustering.go:23-28): the SONAR_DTW_METRIC_* values.
+type DistanceMetric int
+
+const (
+	EuclideanDistance DistanceMetric = iota
+	ManhattanDistance
+	CosineDistance
+	PearsonDistance
+	MahalanobisDistance
+)
+
+// applyStepPattern's names (dtw.go:137-162) in SONAR_DTW_STEP_* order.
+var dtwStepPatterns = []string{"symmetric2", "asymmetric", "symmetric1"}
+
+// DTWWithParams = NewDTWAlignmentWithParams(band, stepPattern, metric).Align(q, r) (dtw.go:45-52).
+// An unknown stepPattern fails as Align does, after the empty-sequence check.
+func (x *Context) DTWWithParams(q, r [][]float64, band int, stepPattern string, metric DistanceMetric,
+	wantCost bool) (*DTWResult, error) {
+	if len(q) == 0 || len(r) == 0 {
+		return nil, fmt.Errorf("empty sequences provided: %w", ErrEmpty)
+	}
+	step := -1
+	for i, s := range dtwStepPatterns {
+		if s == stepPattern {
+			step = i
+		}
+	}
+	if step < 0 {
+		return nil, fmt.Errorf("failed to fill cost matrix: unknown step pattern: %s: %w", stepPattern, ErrInvalid)
+	}
+	qf, d := rows2(q)
+	rf, _ := rows2(r)
+	cap := len(q) + len(r)
+	pq, pr := make([]C.int32_t, cap), make([]C.int32_t, cap)
+	pc := make([]float64, cap)
+	var dist C.double
+	var plen C.int64_t
+	var cost []float64
+	var costp *C.double
+	if wantCost {
+		cost = make([]float64, len(q)*(len(r)+1))
+		costp = f64p(cost)
+	}
+	rc := C.sonar_dtw_params(x.c, f64p(qf), C.int64_t(len(q)), f64p(rf), C.int64_t(len(r)), C.int32_t(d),
+		C.int32_t(band), C.int32_t(step), C.int32_t(metric), &dist, &pq[0], &pr[0], f64p(pc), &plen, costp, 0)
+	if rc != C.SONAR_OK {
+		return nil, x.err(rc)
+	}
+	res := &DTWResult{Distance: float64(dist), PathQuery: make([]int, plen), PathRef: make([]int, plen),
+		PathCost: pc[:plen]}
+	for i := 0; i < int(plen); i++ {
+		res.PathQuery[i], res.PathRef[i] = int(pq[i]), int(pr[i])
+	}
+	if wantCost {
+		res.CostMatrix = split(cost, len(q), len(r)+1)
+	}
+	return res, nil
+}
+
+// DTWQuality = DTWAlignment.GetAlignmentQuality (dtw.go:253-286) of a result for sequences of
+// queryLen and refLen rows; an empty map for a nil result or an empty path, as in Go.  Host only.
+func DTWQuality(res *DTWResult, queryLen, refLen int) map[string]float64 {
+	if res == nil || len(res.PathQuery) == 0 {
+		return map[string]float64{}
+	}
+	n := len(res.PathQuery)
+	pq, pr := make([]C.int32_t, n), make([]C.int32_t, n)
+	for i := 0; i < n; i++ {
+		pq[i], pr[i] = C.int32_t(res.PathQuery[i]), C.int32_t(res.PathRef[i])
+	}
+	var out [4]C.double
+	if rc := C.sonar_dtw_quality(&pq[0], &pr[0], f64p(res.PathCost), C.int64_t(n), C.int64_t(queryLen),
+		C.int64_t(refLen), C.double(res.Distance), &out[0]); rc != C.SONAR_OK {
+		return map[string]float64{}
+	}
+	return map[string]float64{"path_efficiency": float64(out[0]), "diagonal_ratio": float64(out[1]),
+		"average_cost": float64(out[2]), "normalized_distance": float64(out[3])}
+}
+
+// OptimizeStepPattern = DTWAlignment.OptimizeStepPattern (dtw.go:288-311) for a DTWAlignment with
+// this band and metric: the pattern with the smallest Distance (strict <, from "symmetric2").
+func (x *Context) OptimizeStepPattern(q, r [][]float64, band int, metric DistanceMetric) (string, error) {
+	if len(q) == 0 || len(r) == 0 {
+		return dtwStepPatterns[0], nil // every Align fails: Go returns "symmetric2", nil
+	}
+	qf, d := rows2(q)
+	rf, _ := rows2(r)
+	var best C.int32_t
+	rc := C.sonar_dtw_optimize_step_pattern(x.c, f64p(qf), C.int64_t(len(q)), f64p(rf), C.int64_t(len(r)),
+		C.int32_t(d), C.int32_t(band), C.int32_t(metric), 0, &best, nil)
+	if rc != C.SONAR_OK {
+		return dtwStepPatterns[0], x.err(rc)
+	}
+	return dtwStepPatterns[best], nil
+}
+
 // CorrelationResult mirrors the fields of stats.CorrelationResult (correlation.go:44-70) the alignment code reads.
 type CorrelationResult struct {
 	Correlations                                  []float64

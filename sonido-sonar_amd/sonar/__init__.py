@@ -5,6 +5,7 @@ sonido-sonar_amd/lib/libsonar_gpu.so).  Names and argument meaning follow the
 Go reference (RyanBlaney/sonido-sonar) so that tests read like the reference's
 API:  ``Context.fingerprint`` ~ ComputeSTFTWithWindow + MFCC.ComputeFrames,
 ``Context.ncc`` ~ CrossCorrelation.Compute, ``Context.dtw`` ~ DTWAlignment.Align,
+``Context.dtw_params`` ~ NewDTWAlignmentWithParams(...).Align, ``dtw_quality`` ~ GetAlignmentQuality,
 ``Context.generate_fingerprint`` ~ FingerprintGenerator.GenerateFingerprint,
 ``Context.align_features`` ~ AlignmentExtractor.ExtractAlignmentFeatures.
 
@@ -24,6 +25,9 @@ from ._abi import (  # noqa: F401
     multi_shard,
     WINDOWS,
     abi_version,
+    dtw_quality,
+    DTW_STEPS,
+    DTW_METRICS,
     build,
     lib,
     stft_frames,

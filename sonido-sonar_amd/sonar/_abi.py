@@ -23,6 +23,11 @@ WINDOWS = {"hann": 0, "hamming": 1, "blackman": 2, "blackman_harris": 3, "kaiser
            "tukey": 5, "rectangular": 6, "bartlett": 7, "welch": 8}
 SPECTRAL_NAMES = ["centroid", "rolloff", "bandwidth", "flatness", "crest", "slope", "flux",
                   "low_ratio", "high_ratio"]
+# NewDTWAlignmentWithParams' step patterns and metrics (SONAR_DTW_STEP_* / SONAR_DTW_METRIC_*)
+DTW_STEPS = {"symmetric2": 0, "asymmetric": 1, "symmetric1": 2}
+DTW_STEP_NAMES = ["symmetric2", "asymmetric", "symmetric1"]
+DTW_METRICS = {"euclidean": 0, "manhattan": 1, "cosine": 2, "pearson": 3, "mahalanobis": 4}
+DTW_QUALITY_KEYS = ["path_efficiency", "diagonal_ratio", "average_cost", "normalized_distance"]
 NCC_KEYS = ["peak_correlation", "peak_lag", "peak_index", "p_value", "snr", "sharpness",
             "second_peak", "peak_to_sidelobe", "overlap_length", "num_lags"]
 
@@ -218,6 +223,11 @@ def lib():
                                                  C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_dtw.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, _d, _vp, _vp, _vp, _i64p,
                             _vp, C.c_int32]
+    L.sonar_dtw_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   _d, _vp, _vp, _vp, _i64p, _vp, C.c_int32]
+    L.sonar_dtw_quality.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_double, _d]
+    L.sonar_dtw_optimize_step_pattern.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, _i32p, _d]
     L.sonar_fingerprint_config_default.argtypes = [C.POINTER(FingerprintConfig)]
     L.sonar_fingerprint_config_default.restype = None
     L.sonar_generate_fingerprint.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_char_p,
@@ -303,6 +313,37 @@ def _formant_dict(recs, F):
 
 def abi_version():
     return lib().sonar_abi_version()
+
+
+def dtw_quality(res, nq, nr):
+    """DTWAlignment.GetAlignmentQuality of a dtw / dtw_params result (sonar_dtw_quality, host only):
+    path_efficiency, diagonal_ratio, average_cost, normalized_distance.  An empty path raises
+    (ERR_EMPTY; Go returns an empty map)."""
+    pq = np.ascontiguousarray(res["path_q"], dtype=np.int32)
+    pr = np.ascontiguousarray(res["path_r"], dtype=np.int32)
+    pc = np.ascontiguousarray(res["path_cost"], dtype=np.float64)
+    out = (C.c_double * 4)()
+    rc = lib().sonar_dtw_quality(_ptr(pq), _ptr(pr), _ptr(pc), len(pq), nq, nr, float(res["distance"]), out)
+    if rc != OK:
+        raise SonarError(rc, "empty alignment path" if rc == ERR_EMPTY else "invalid argument")
+    return dict(zip(DTW_QUALITY_KEYS, out))
+
+
+def _dtw_step(step, empty=False):
+    """SONAR_DTW_STEP_* of a step-pattern name; an int passes through (unknown values reach the
+    library, which answers with Go's error and the value).  An unknown name raises Go's error with
+    the name, unless a sequence is empty: that error comes first, from the library."""
+    if not isinstance(step, str):
+        return int(step)
+    if step not in DTW_STEPS and not empty:
+        raise SonarError(ERR_INVALID, f"failed to fill cost matrix: unknown step pattern: {step}")
+    return DTW_STEPS.get(step, -1)
+
+
+def _dtw_metric(metric):
+    if isinstance(metric, str):
+        return DTW_METRICS[metric]
+    return int(metric)
 
 
 def stft_frames(n, W, H):
@@ -757,6 +798,62 @@ class Context:
                                       _ptr(cost) if want_cost else None, 0))
         P = plen.value
         return {"distance": dist.value, "path_q": pq[:P], "path_r": pr[:P], "path_cost": pc[:P], "cost": cost}
+
+    def dtw_params(self, q, r, band=-1, step="symmetric2", metric="euclidean", want_cost=False):
+        """NewDTWAlignmentWithParams(band, step, metric).Align (sonar_dtw_params): the dict of dtw.
+        step: "symmetric2" | "asymmetric" | "symmetric1"; metric: "euclidean" | "manhattan" |
+        "cosine" | "pearson" | "mahalanobis" (= Euclidean, as in Go), or the SONAR_DTW_* values."""
+        q, r = _f64(q), _f64(r)
+        if q.ndim == 1:
+            q = q[:, None]
+        if r.ndim == 1:
+            r = r[:, None]
+        nq, d = q.shape if q.size else (0, 1)
+        nr = r.shape[0] if r.size else 0
+        cap = nq + nr + 1
+        pq, pr, pc = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap)
+        plen, dist = C.c_int64(), C.c_double()
+        cost = np.zeros((nq, nr + 1)) if want_cost else None
+        self._check(self._L.sonar_dtw_params(self._h, _ptr(q) if nq else None, nq, _ptr(r) if nr else None, nr, d,
+                                             band, _dtw_step(step, not (nq and nr)), _dtw_metric(metric),
+                                             C.byref(dist), _ptr(pq),
+                                             _ptr(pr), _ptr(pc), C.byref(plen), _ptr(cost) if want_cost else None, 0))
+        P = plen.value
+        return {"distance": dist.value, "path_q": pq[:P], "path_r": pr[:P], "path_cost": pc[:P], "cost": cost}
+
+    def dtw_params_device(self, q_ptr, nq, r_ptr, nr, dim, path_q_ptr, path_r_ptr, path_cost_ptr, band=-1,
+                          step="symmetric2", metric="euclidean", cost_ptr=None):
+        """dtw_params on device memory (device_ptrs = 1): q, r, the path arrays (capacity nq + nr)
+        and the optional nq x (nr + 1) cost matrix are device addresses -> (distance, path length)."""
+        plen, dist = C.c_int64(), C.c_double()
+        self._check(self._L.sonar_dtw_params(self._h, q_ptr, nq, r_ptr, nr, dim, band,
+                                             _dtw_step(step, not (nq > 0 and nr > 0 and q_ptr and r_ptr)),
+                                             _dtw_metric(metric), C.byref(dist), path_q_ptr, path_r_ptr,
+                                             path_cost_ptr, C.byref(plen), cost_ptr, 1))
+        return dist.value, plen.value
+
+    def dtw_optimize_step_pattern(self, q, r, band=-1, metric="euclidean"):
+        """DTWAlignment.OptimizeStepPattern (sonar_dtw_optimize_step_pattern) -> (best pattern's
+        name, {pattern: distance}; NaN for a pattern whose Align failed)."""
+        q, r = _f64(q), _f64(r)
+        if q.ndim == 1:
+            q = q[:, None]
+        if r.ndim == 1:
+            r = r[:, None]
+        nq, d = q.shape if q.size else (0, 1)
+        nr = r.shape[0] if r.size else 0
+        best, d3 = C.c_int32(), (C.c_double * 3)()
+        self._check(self._L.sonar_dtw_optimize_step_pattern(self._h, _ptr(q) if nq else None, nq,
+                                                            _ptr(r) if nr else None, nr, d, band, _dtw_metric(metric),
+                                                            0, C.byref(best), d3))
+        return DTW_STEP_NAMES[best.value], dict(zip(DTW_STEP_NAMES, d3))
+
+    def dtw_optimize_step_pattern_device(self, q_ptr, nq, r_ptr, nr, dim, band=-1, metric="euclidean"):
+        """dtw_optimize_step_pattern on device memory (device_ptrs = 1): q and r are device addresses."""
+        best, d3 = C.c_int32(), (C.c_double * 3)()
+        self._check(self._L.sonar_dtw_optimize_step_pattern(self._h, q_ptr, nq, r_ptr, nr, dim, band,
+                                                            _dtw_metric(metric), 1, C.byref(best), d3))
+        return DTW_STEP_NAMES[best.value], dict(zip(DTW_STEP_NAMES, d3))
 
     # -- Go API mirror -----------------------------------------------------
     def _result(self, h):
