@@ -23,6 +23,9 @@
  *                                 ChromaSTFT.ComputeChroma (algorithms/chroma/chroma_stft.go:45)
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
+ *   sonar_xcorr_params         <- CrossCorrelation.Compute for every type, method and constructor
+ *                                 (correlation.go:103-128, 131-370, 412-418, 726-774)
+ *   sonar_autocorr             <- AutoCorrelation.Compute / SetParameters (correlation.go:669-690)
  *   sonar_dtw                  <- DTWAlignment.Align (algorithms/stats/dtw.go:55)
  *   sonar_dtw_params           <- NewDTWAlignmentWithParams(...).Align (dtw.go:45-52, 137-162; distance.go)
  *   sonar_dtw_quality          <- DTWAlignment.GetAlignmentQuality (dtw.go:253-286)
@@ -291,6 +294,42 @@ int sonar_chroma_stft(sonar_ctx* ctx, const double* pcm, int64_t n, int64_t n_fr
  *  peak_to_sidelobe, overlap_length, num_lags} (correlation.go:131-200). */
 int sonar_ncc(sonar_ctx* ctx, const double* a, int64_t na, const double* b, int64_t nb,
               int32_t max_lag, double* corr, double* metrics, int32_t device_ptrs);
+
+/* ---- cross-correlation in full: CrossCorrelation.Compute (correlation.go:131-200) for every
+ * correlation type, method and constructor; sonar_ncc above is the one instance
+ * NewCrossCorrelationWithParams(maxLag, NormalizedCrossCorrelation, TimeDomain).
+ * corr_type and method are CorrelationType's and CorrelationMethod's values (:12-41).  use_fft is
+ * the private field the constructors set: NewCrossCorrelation(maxLag) is {PEARSON, TIME_DOMAIN,
+ * use_fft 1}; NewCrossCorrelationWithParams(maxLag, type, method) is use_fft = (method ==
+ * FREQUENCY_DOMAIN); NewAutoCorrelation(maxLag) with SetParameters(type, method) keeps use_fft 1.
+ * As in Compute: empty inputs are SONAR_ERR_EMPTY "empty signals provided"; with use_fft and more
+ * than 1,000 samples in either input the method becomes FREQUENCY_DOMAIN (:139-142); a method that
+ * is then none of the three is SONAR_ERR_INVALID "unsupported correlation method"; SLIDING_WINDOW
+ * is TIME_DOMAIN (:294-297).  Both inputs are z-scored first (normalize :464-501) under every
+ * method.  corr has 2L+1 entries, L = max(0, min(max_lag, na-1, nb-1)).
+ * TIME_DOMAIN, per lag: PEARSON pearsonCorrelation (:314-370: overlap means, centred sums, 0 when
+ * the overlap is <= 1 sample or the denominator < 1e-10, clamped to [-1, 1]); SPEARMAN, KENDALL and
+ * every unknown type are PEARSON (:301-310); NCC as sonar_ncc, bit for bit; ZNCC the NCC of the
+ * z-scores after subtractMean (:412-418, 504-523).
+ * FREQUENCY_DOMAIN (computeFFT :231-291) does not consult the type: corr[i] is the un-normalised
+ * circular sum real(ifft(fft(a) * conj(fft(b))))[lag or N + lag], N = nextPowerOf2(na + nb - 1), with
+ * Go's recursive radix-2 transform (:726-774) bit for bit.  The peak is then of the order of the
+ * overlap length, and calculatePValue's sqrt(1 - peak^2) is NaN: p_value 0.5.  Limit: na + nb - 1
+ * <= 4,194,304 (N <= 2^22), beyond it SONAR_ERR_UNSUPPORTED; TIME_DOMAIN has no limit.  The first
+ * call at a given N builds its twiddle table (cached in the context until sonar_trim).
+ * metrics[12] = sonar_ncc's ten, then the method that ran (after the switch) and corr_type as given.
+ * Host or device pointers (device_ptrs); with device pointers a null corr goes to library scratch. */
+enum { SONAR_CORR_PEARSON = 0, SONAR_CORR_SPEARMAN = 1, SONAR_CORR_KENDALL = 2,
+       SONAR_CORR_NCC = 3, SONAR_CORR_ZNCC = 4 };
+enum { SONAR_CORR_TIME_DOMAIN = 0, SONAR_CORR_FREQUENCY_DOMAIN = 1, SONAR_CORR_SLIDING_WINDOW = 2 };
+int sonar_xcorr_params(sonar_ctx* ctx, const double* a, int64_t na, const double* b, int64_t nb,
+                       int32_t max_lag, int32_t corr_type, int32_t method, int32_t use_fft,
+                       double* corr, double* metrics /*[12]*/, int32_t device_ptrs);
+/* AutoCorrelation.Compute (:669-690) = Compute(x, x) of NewCrossCorrelation(max_lag) after
+ * SetParameters(corr_type, method): use_fft stays 1, so above 1,000 samples it is always the FFT
+ * method.  The one input is transformed once. */
+int sonar_autocorr(sonar_ctx* ctx, const double* x, int64_t n, int32_t max_lag, int32_t corr_type,
+                   int32_t method, double* corr, double* metrics /*[12]*/, int32_t device_ptrs);
 
 /* ---- path B: DTW (float64, optional Sakoe-Chiba band).  sonar_dtw is the default
  * DTWAlignment (Euclidean, symmetric2); sonar_dtw_params takes NewDTWAlignmentWithParams'

@@ -241,6 +241,31 @@ int launch_ncc(const double* a, int64_t na, const double* b, int64_t nb, int64_t
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+// launch_ncc's kernels one by one (sonar_xcorr_params: the same z-score under every type and method)
+int launch_ncc_stats(const double* a, int64_t na, const double* b, int64_t nb, double* stats, hipStream_t s) {
+  const NccJob* none = nullptr;
+  hipLaunchKernelGGL((ncc_stats_kernel<false>), dim3(2), dim3(64), 0, s, a, na, b, nb, stats, none);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_ncc_zscore(const double* a, int64_t na, const double* b, int64_t nb, double* xa, double* xb, double* stats,
+                      hipStream_t s) {
+  const NccJob* none = nullptr;
+  hipLaunchKernelGGL((ncc_stats_kernel<false>), dim3(2), dim3(64), 0, s, a, na, b, nb, stats, none);
+  const int64_t nmax = na > nb ? na : nb;
+  hipLaunchKernelGGL((ncc_norm_kernel<false>), dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, s, a, na, b, nb, stats, xa,
+                     xb, none);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_ncc_lags(const double* xa, int64_t na, const double* xb, int64_t nb, int64_t L, double* corr, hipStream_t s) {
+  const NccJob* none = nullptr;
+  const int64_t nl = 2 * L + 1;
+  hipLaunchKernelGGL((ncc_lag_kernel<false>), dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, xa, na, xb, nb, L, corr,
+                     none);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
 // launch_ncc over many pairs in three launches (blockIdx.y = pair); the same kernels, arithmetic
 // and order per pair, so the same bits
 int launch_ncc_batch(const NccJob* hjobs, const NccJob* djobs, int nj, hipStream_t s) {

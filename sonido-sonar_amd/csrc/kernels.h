@@ -209,6 +209,27 @@ struct NccJob {
 int launch_ncc_batch(const NccJob* hjobs, const NccJob* djobs, int nj, hipStream_t s);
 int launch_ncc(const double* a, int64_t na, const double* b, int64_t nb, int64_t L, double* norm_a,
                double* norm_b, double* stats, double* corr, hipStream_t s);
+// launch_ncc's three kernels one by one, for sonar_xcorr_params (xcorr_api.cpp): the sequential
+// mean / std of both inputs into stats[0..3]; those plus the z-score (normalize :464-501) into
+// norm_a / norm_b; the NCC lag sums of two prepared arrays
+int launch_ncc_stats(const double* a, int64_t na, const double* b, int64_t nb, double* stats, hipStream_t s);
+int launch_ncc_zscore(const double* a, int64_t na, const double* b, int64_t nb, double* norm_a, double* norm_b,
+                      double* stats, hipStream_t s);
+int launch_ncc_lags(const double* xa, int64_t na, const double* xb, int64_t nb, int64_t L, double* corr, hipStream_t s);
+// CrossCorrelation.Compute's other configurations (xcorr_kernels.hip; correlation.go:231-370, 412-418,
+// 726-774).  Every sum in Go's index order, unfused.
+// pearsonCorrelation per lag (:314-370) of two z-scored arrays: corr[2L + 1]
+int launch_xcorr_pearson(const double* xa, int64_t na, const double* xb, int64_t nb, int64_t L, double* corr,
+                         hipStream_t s);
+// subtractMean (:504-523) of both arrays in place, the means from launch_ncc_stats (stats[0], stats[2])
+int launch_xcorr_center(double* xa, int64_t na, double* xb, int64_t nb, const double* stats, hipStream_t s);
+// computeFFT (:231-291) of two z-scored arrays: N = nextPowerOf2(na + nb - 1) <= XCORR_FFT_MAX_N, tw = the
+// N / 2 (cos, sin) pairs of -2 pi m / N (xcorr_twiddles), A / B / C = N complex doubles each of scratch
+// (B unused when xb == xa && nb == na: one transform serves both), corr[2L + 1] = re(C[lag or N + lag]) / N
+constexpr int64_t XCORR_FFT_MAX_N = int64_t(1) << 22;
+constexpr int XCORR_FFT_TILE = 4096;   // points whose low levels run in LDS (64 KB)
+int launch_xcorr_fft(const double* xa, int64_t na, const double* xb, int64_t nb, int64_t N, const double2* tw,
+                     double2* A, double2* B, double2* C, int64_t L, double* corr, hipStream_t s);
 // AlignmentAnalyzer.addNoise and flatten2DFeatures (align_kernels.hip)
 int launch_perturb(const double* q, int64_t nq, int dim, double level, double* out, hipStream_t s);
 int launch_first_column(const double* x, int64_t n, int dim, double* out, hipStream_t s);

@@ -1,0 +1,150 @@
+// xcorr_api.cpp -- sonar_xcorr_params / sonar_autocorr: CrossCorrelation.Compute and
+// AutoCorrelation.Compute (algorithms/stats/correlation.go:131-200, 669-690) for every correlation
+// type, method and constructor.  The kernels are xcorr_kernels.hip's (Pearson per lag, subtractMean,
+// the FFT method) and align_kernels.hip's (z-score, NCC lag sums); the peak, p-value and quality
+// metrics are host::ncc_metrics, as in sonar_ncc.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ctx.h"
+#include "host_dsp.h"
+#include "kernels.h"
+
+using sonar::detail::dbuf;
+using sonar::detail::fail;
+using sonar::detail::timed_begin;
+using sonar::detail::timed_end;
+
+namespace {
+
+// nextPowerOf2 (correlation.go:713-723)
+int64_t next_pow2(int64_t n) {
+  int64_t p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// The (cos, sin) pairs of -2 pi m / N, m < N / 2, on the device: the twiddles of fft's top level
+// (:748), which serve every level by stride (xcorr_kernels.hip).  libm on the host, as the checker and the oracle.
+// Built once per N and context; the table is a cached buffer, so sonar_trim releases it.
+const double2* xcorr_twiddles(sonar_ctx* c, int64_t N) {
+  const std::string name = "xcorr.tw." + std::to_string(N);
+  auto it = c->bufs.find(name);
+  if (it != c->bufs.end() && it->second.ptr) return (const double2*)it->second.ptr;
+  const int64_t half = N / 2;
+  void* d = dbuf(c, name, (size_t)std::max<int64_t>(half, 1) * sizeof(double2));
+  if (!d) { c->bufs.erase(name); return nullptr; }
+  std::vector<double2> h((size_t)half);
+  for (int64_t m = 0; m < half; ++m) {
+    // one sincos call, as the oracle's cos(th), sin(th) pair compiles to: glibc's sincos and its
+    // sin / cos differ in the last bit for a few angles
+    ::sincos(-2.0 * M_PI * (double)m / (double)N, &h[(size_t)m].y, &h[(size_t)m].x);
+  }
+  if (half > 0 && (hipMemcpyAsync(d, h.data(), (size_t)half * sizeof(double2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                   hipStreamSynchronize(c->stream) != hipSuccess)) {
+    hipFree(d);
+    c->bufs.erase(name);
+    return nullptr;
+  }
+  return (const double2*)d;
+}
+
+// Compute (:131-200).  same: signal2 is signal1 (AutoCorrelation.Compute :682-684)
+int xcorr_run(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_t nb, int32_t max_lag, int32_t corr_type,
+              int32_t method, int32_t use_fft, double* corr, double* metrics, int32_t device_ptrs, bool same) {
+  if (!c) return SONAR_ERR_INVALID;
+  if (na <= 0 || nb <= 0 || !a || !b) return fail(c, SONAR_ERR_EMPTY, "empty signals provided");
+  constexpr int64_t kFftThreshold = 1000;                         // fftThreshold in every constructor
+  if (use_fft && (na > kFftThreshold || nb > kFftThreshold)) method = SONAR_CORR_FREQUENCY_DOMAIN;   // :139-142
+  if (method != SONAR_CORR_TIME_DOMAIN && method != SONAR_CORR_FREQUENCY_DOMAIN && method != SONAR_CORR_SLIDING_WINDOW)
+    return fail(c, SONAR_ERR_INVALID, "unsupported correlation method");
+  const bool fft = method == SONAR_CORR_FREQUENCY_DOMAIN;
+  int64_t N = 0;
+  if (fft) {
+    if (na + nb - 1 > sonar::XCORR_FFT_MAX_N)
+      return fail(c, SONAR_ERR_UNSUPPORTED, "frequency-domain correlation: len(signal1) + len(signal2) - 1 = " +
+                                                std::to_string(na + nb - 1) + " exceeds the FFT limit of " +
+                                                std::to_string(sonar::XCORR_FFT_MAX_N) + " points");
+    N = next_pow2(na + nb - 1);
+  }
+  int64_t L = max_lag;                                            // calculateActualMaxLag :452-461
+  L = std::min<int64_t>(L, na - 1);
+  L = std::min<int64_t>(L, nb - 1);
+  L = std::max<int64_t>(L, 0);
+  const int64_t nl = 2 * L + 1;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const double *da = a, *db = b;
+  if (!device_ptrs) {
+    double* pa = (double*)dbuf(c, "xcorr.a", na * 8);
+    double* pb = same ? pa : (double*)dbuf(c, "xcorr.b", nb * 8);
+    if (!pa || !pb) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+    HIP_TRY(c, hipMemcpyAsync(pa, a, na * 8, hipMemcpyHostToDevice, s));
+    if (!same) HIP_TRY(c, hipMemcpyAsync(pb, b, nb * 8, hipMemcpyHostToDevice, s));
+    da = pa; db = pb;
+  }
+  double* xa = (double*)dbuf(c, "xcorr.xa", na * 8);
+  double* xb = (double*)dbuf(c, "xcorr.xb", nb * 8);
+  double* st = (double*)dbuf(c, "xcorr.stats", 128);              // [0..3] z-score, [8..11] subtractMean
+  double* dc = (device_ptrs && corr) ? corr : (double*)dbuf(c, "xcorr.corr", nl * 8);
+  if (!xa || !xb || !st || !dc) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+  const double2* tw = nullptr;
+  double2 *A = nullptr, *B = nullptr, *C = nullptr;
+  if (fft) {
+    tw = xcorr_twiddles(c, N);
+    A = (double2*)dbuf(c, "xcorr.fa", (size_t)N * sizeof(double2));
+    B = same ? A : (double2*)dbuf(c, "xcorr.fb", (size_t)N * sizeof(double2));
+    C = (double2*)dbuf(c, "xcorr.fc", (size_t)N * sizeof(double2));
+    if (!tw || !A || !B || !C) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (correlation FFT)");
+  }
+  hipEvent_t tend = timed_begin(c, s);
+  int rc = sonar::launch_ncc_zscore(da, na, db, nb, xa, xb, st, s);   // normalizeInputs is true in every constructor
+  if (rc == 0) {
+    if (fft) {                                                    // computeFFT: the type is not consulted
+      rc = sonar::launch_xcorr_fft(xa, na, same ? xa : xb, nb, N, tw, A, B, C, L, dc, s);
+    } else if (corr_type == SONAR_CORR_NCC) {
+      rc = sonar::launch_ncc_lags(xa, na, xb, nb, L, dc, s);
+    } else if (corr_type == SONAR_CORR_ZNCC) {
+      rc = sonar::launch_ncc_stats(xa, na, xb, nb, st + 8, s);
+      if (rc == 0) rc = sonar::launch_xcorr_center(xa, na, xb, nb, st + 8, s);
+      if (rc == 0) rc = sonar::launch_ncc_lags(xa, na, xb, nb, L, dc, s);
+    } else {                                                      // Pearson, Spearman, Kendall, unknown (:301-310)
+      rc = sonar::launch_xcorr_pearson(xa, na, xb, nb, L, dc, s);
+    }
+  }
+  if (rc != 0) return fail(c, SONAR_ERR_DEVICE, "correlation launch failed");
+  timed_end(c, s, tend);
+  std::vector<double> hc((size_t)nl);
+  HIP_TRY(c, hipMemcpyAsync(hc.data(), dc, nl * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (corr && !device_ptrs) std::memcpy(corr, hc.data(), nl * 8);
+  if (metrics) {
+    const auto m = sonar::host::ncc_metrics(hc.data(), nl, L, na, nb);
+    const double v[12] = {m.peak_corr, (double)m.peak_lag, (double)m.peak_index, m.p_value, m.snr, m.sharpness,
+                          m.second_peak, m.psl, (double)m.overlap, (double)m.num_lags, (double)method,
+                          (double)corr_type};
+    std::memcpy(metrics, v, sizeof(v));
+  }
+  return SONAR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sonar_xcorr_params(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_t nb, int32_t max_lag,
+                       int32_t corr_type, int32_t method, int32_t use_fft, double* corr, double* metrics,
+                       int32_t device_ptrs) {
+  return xcorr_run(c, a, na, b, nb, max_lag, corr_type, method, use_fft, corr, metrics, device_ptrs,
+                   a == b && na == nb);
+}
+
+int sonar_autocorr(sonar_ctx* c, const double* x, int64_t n, int32_t max_lag, int32_t corr_type, int32_t method,
+                   double* corr, double* metrics, int32_t device_ptrs) {
+  return xcorr_run(c, x, n, x, n, max_lag, corr_type, method, 1, corr, metrics, device_ptrs, true);
+}
+
+}  // extern "C"

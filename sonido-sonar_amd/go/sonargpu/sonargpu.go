@@ -699,13 +699,124 @@ func (x *Context) OptimizeStepPattern(q, r [][]float64, band int, metric Distanc
 	return dtwStepPatterns[best], nil
 }
 
-// CorrelationResult mirrors the fields of stats.CorrelationResult (correlation.go:44-70) the alignment code reads.
+// CorrelationResult mirrors stats.CorrelationResult (correlation.go:44-70).  NCC fills the fields the
+// alignment code reads; CrossCorrelation.Compute and AutoCorrelation.Compute fill all of them (PSL is
+// PeakToSidelobe).
 type CorrelationResult struct {
 	Correlations                                  []float64
+	Lags                                          []int
 	PeakCorrelation                               float64
 	PeakLag, PeakIndex                            int
 	PValue, SNR, Sharpness, SecondPeak, PSL       float64
+	IsSignificant                                 bool
+	ConfidenceLevel                               float64
+	Method                                        CorrelationMethod
+	Type                                          CorrelationType
+	MaxLag                                        int
 	OverlapLength                                 int
+	ComputationTime                               float64
+}
+
+// CorrelationType and CorrelationMethod mirror stats.CorrelationType / stats.CorrelationMethod
+// (correlation.go:9-41): the SONAR_CORR_* values.
+type CorrelationType int
+type CorrelationMethod int
+
+const (
+	Pearson CorrelationType = iota
+	Spearman
+	Kendall
+	NormalizedCrossCorrelation
+	ZeroNormalizedCrossCorrelation
+)
+
+const (
+	TimeDomain CorrelationMethod = iota
+	FrequencyDomain
+	SlidingWindow
+)
+
+// CrossCorrelation mirrors stats.CrossCorrelation (correlation.go:87-100) on a Context: the three
+// fields its constructors set differently.  confidenceLevel 0.95, minStdDev 1e-10, normalizeInputs
+// true and fftThreshold 1000 are the same in every constructor and live in the library.
+type CrossCorrelation struct {
+	x               *Context
+	maxLag          int
+	correlationType CorrelationType
+	method          CorrelationMethod
+	useFFT          bool
+}
+
+// NewCrossCorrelation = stats.NewCrossCorrelation(maxLag) (:103-114): Pearson, TimeDomain, useFFT true
+// -- above 1,000 samples Compute runs the FFT method (un-normalised sums, DESIGN F19).
+func (x *Context) NewCrossCorrelation(maxLag int) *CrossCorrelation {
+	return &CrossCorrelation{x: x, maxLag: maxLag, correlationType: Pearson, method: TimeDomain, useFFT: true}
+}
+
+// NewCrossCorrelationWithParams = stats.NewCrossCorrelationWithParams (:117-128): useFFT = method == FrequencyDomain.
+func (x *Context) NewCrossCorrelationWithParams(maxLag int, corrType CorrelationType,
+	method CorrelationMethod) *CrossCorrelation {
+	return &CrossCorrelation{x: x, maxLag: maxLag, correlationType: corrType, method: method,
+		useFFT: method == FrequencyDomain}
+}
+
+// Compute = CrossCorrelation.Compute (:131-200) through sonar_xcorr_params.
+func (cc *CrossCorrelation) Compute(signal1, signal2 []float64) (*CorrelationResult, error) {
+	if len(signal1) == 0 || len(signal2) == 0 {
+		return nil, fmt.Errorf("empty signals provided: %w", ErrEmpty)
+	}
+	L := cc.maxLag // calculateActualMaxLag :452-461
+	if len(signal1)-1 < L {
+		L = len(signal1) - 1
+	}
+	if len(signal2)-1 < L {
+		L = len(signal2) - 1
+	}
+	if L < 0 {
+		L = 0
+	}
+	corr := make([]float64, 2*L+1)
+	var m [12]float64
+	useFFT := C.int32_t(0)
+	if cc.useFFT {
+		useFFT = 1
+	}
+	if rc := C.sonar_xcorr_params(cc.x.c, f64p(signal1), C.int64_t(len(signal1)), f64p(signal2),
+		C.int64_t(len(signal2)), C.int32_t(cc.maxLag), C.int32_t(cc.correlationType), C.int32_t(cc.method), useFFT,
+		f64p(corr), (*C.double)(unsafe.Pointer(&m[0])), 0); rc != C.SONAR_OK {
+		return nil, cc.x.err(rc)
+	}
+	lags := make([]int, len(corr))
+	for i := range lags {
+		lags[i] = i - L
+	}
+	return &CorrelationResult{Correlations: corr, Lags: lags, PeakCorrelation: m[0], PeakLag: int(m[1]),
+		PeakIndex: int(m[2]), PValue: m[3], IsSignificant: m[3] < 1.0-0.95, ConfidenceLevel: 0.95, SNR: m[4],
+		Sharpness: m[5], SecondPeak: m[6], PSL: m[7], Method: CorrelationMethod(int(m[10])),
+		Type: cc.correlationType, MaxLag: cc.maxLag, OverlapLength: int(m[8]), ComputationTime: 0}, nil
+}
+
+// AutoCorrelation mirrors stats.AutoCorrelation (correlation.go:669-690).
+type AutoCorrelation struct {
+	crossCorr *CrossCorrelation
+}
+
+// NewAutoCorrelation = stats.NewAutoCorrelation(maxLag): a NewCrossCorrelation(maxLag) inside.
+func (x *Context) NewAutoCorrelation(maxLag int) *AutoCorrelation {
+	return &AutoCorrelation{crossCorr: x.NewCrossCorrelation(maxLag)}
+}
+
+// SetParameters = AutoCorrelation.SetParameters (:687-690): type and method only; useFFT stays true, so
+// no method keeps Compute in the time domain above 1,000 samples (DESIGN F21).
+func (ac *AutoCorrelation) SetParameters(corrType CorrelationType, method CorrelationMethod) {
+	ac.crossCorr.correlationType = corrType
+	ac.crossCorr.method = method
+}
+
+// Compute = AutoCorrelation.Compute (:682-684) = crossCorr.Compute(signal, signal); the library sees one
+// array twice and transforms it once.
+func (ac *AutoCorrelation) Compute(signal []float64) (*CorrelationResult, error) {
+	return ac.crossCorr.Compute(signal, signal)
 }
 
 // NCC = CrossCorrelation{NormalizedCrossCorrelation, TimeDomain, maxLag}.Compute(s1, s2).

@@ -4,7 +4,8 @@ Thin ctypes binding over the C ABI in include/sonar_gpu.h (library
 sonido-sonar_amd/lib/libsonar_gpu.so).  Names and argument meaning follow the
 Go reference (RyanBlaney/sonido-sonar) so that tests read like the reference's
 API:  ``Context.fingerprint`` ~ ComputeSTFTWithWindow + MFCC.ComputeFrames,
-``Context.ncc`` ~ CrossCorrelation.Compute, ``Context.dtw`` ~ DTWAlignment.Align,
+``Context.ncc`` ~ CrossCorrelation.Compute, ``Context.xcorr_params`` / ``xcorr`` / ``autocorr`` ~ the
+same for every type, method and constructor, ``Context.dtw`` ~ DTWAlignment.Align,
 ``Context.dtw_params`` ~ NewDTWAlignmentWithParams(...).Align, ``dtw_quality`` ~ GetAlignmentQuality,
 ``Context.generate_fingerprint`` ~ FingerprintGenerator.GenerateFingerprint,
 ``Context.align_features`` ~ AlignmentExtractor.ExtractAlignmentFeatures.
@@ -28,6 +29,8 @@ from ._abi import (  # noqa: F401
     dtw_quality,
     DTW_STEPS,
     DTW_METRICS,
+    CORR_TYPES,
+    CORR_METHODS,
     build,
     lib,
     stft_frames,
@@ -54,6 +57,7 @@ from ._abi import (  # noqa: F401
     ERR_INVALID,
     ERR_EMPTY,
     ERR_TOO_SHORT,
+    ERR_UNSUPPORTED,
     ERR_PANIC,
     EXPORTED_SYMBOLS,
 )

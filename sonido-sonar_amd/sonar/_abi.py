@@ -28,6 +28,9 @@ DTW_STEPS = {"symmetric2": 0, "asymmetric": 1, "symmetric1": 2}
 DTW_STEP_NAMES = ["symmetric2", "asymmetric", "symmetric1"]
 DTW_METRICS = {"euclidean": 0, "manhattan": 1, "cosine": 2, "pearson": 3, "mahalanobis": 4}
 DTW_QUALITY_KEYS = ["path_efficiency", "diagonal_ratio", "average_cost", "normalized_distance"]
+# CorrelationType / CorrelationMethod (SONAR_CORR_*), correlation.go:12-41
+CORR_TYPES = {"pearson": 0, "spearman": 1, "kendall": 2, "ncc": 3, "zncc": 4}
+CORR_METHODS = {"time": 0, "frequency": 1, "sliding": 2}
 NCC_KEYS = ["peak_correlation", "peak_lag", "peak_index", "p_value", "snr", "sharpness",
             "second_peak", "peak_to_sidelobe", "overlap_length", "num_lags"]
 
@@ -219,6 +222,9 @@ def lib():
     L.sonar_pitch_yin.argtypes = [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int32]
     L.sonar_chroma_stft.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32]
     L.sonar_ncc.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32]
+    L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     _vp, _vp, C.c_int32]
+    L.sonar_autocorr.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_music_alignment_features.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_dtw.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, _d, _vp, _vp, _vp, _i64p,
@@ -338,6 +344,18 @@ def _dtw_step(step, empty=False):
     if step not in DTW_STEPS and not empty:
         raise SonarError(ERR_INVALID, f"failed to fill cost matrix: unknown step pattern: {step}")
     return DTW_STEPS.get(step, -1)
+
+
+def _corr_enum(v, table):
+    """SONAR_CORR_* of a name; an int passes through (unknown values reach the library, as in Go)."""
+    return table[v] if isinstance(v, str) else int(v)
+
+
+def _xcorr_metrics(met):
+    """metrics[12] as a dict: NCC_KEYS, then the method that ran and the type (both ints)."""
+    d = dict(zip(NCC_KEYS, met[:10].tolist()))
+    d["method"], d["type"] = int(met[10]), int(met[11])
+    return d
 
 
 def _dtw_metric(metric):
@@ -780,6 +798,57 @@ class Context:
         self._check(self._L.sonar_voice_quality(self._h, _ptr(x) if len(x) else None, len(x), sample_rate,
                                                 C.byref(q)))
         return {k: getattr(q, k) for k, _ in VoiceQuality._fields_}
+
+    def xcorr_params(self, a, b, max_lag, corr_type="pearson", method="time", use_fft=None):
+        """CrossCorrelation.Compute (sonar_xcorr_params) -> (correlations, lags, metrics dict).
+        corr_type: "pearson" | "spearman" | "kendall" | "ncc" | "zncc"; method: "time" | "frequency"
+        | "sliding"; or the SONAR_CORR_* values.  use_fft None is NewCrossCorrelationWithParams'
+        rule (method == frequency); xcorr() is NewCrossCorrelation, autocorr() NewAutoCorrelation."""
+        a, b = _f64(a), _f64(b)
+        t, m = _corr_enum(corr_type, CORR_TYPES), _corr_enum(method, CORR_METHODS)
+        if use_fft is None:
+            use_fft = m == CORR_METHODS["frequency"]
+        L = max(0, min(max_lag, len(a) - 1, len(b) - 1)) if len(a) and len(b) else 0
+        corr, met = np.zeros(2 * L + 1), np.zeros(12)
+        self._check(self._L.sonar_xcorr_params(self._h, _ptr(a) if len(a) else None, len(a),
+                                               _ptr(b) if len(b) else None, len(b), max_lag, t, m, int(bool(use_fft)),
+                                               _ptr(corr), _ptr(met), 0))
+        return corr, np.arange(-L, L + 1), _xcorr_metrics(met)
+
+    def xcorr(self, a, b, max_lag):
+        """stats.NewCrossCorrelation(max_lag).Compute(a, b): Pearson in the time domain up to 1,000
+        samples, the FFT method's un-normalised sums above."""
+        return self.xcorr_params(a, b, max_lag, "pearson", "time", use_fft=True)
+
+    def autocorr(self, x, max_lag, corr_type="pearson", method="time"):
+        """NewAutoCorrelation(max_lag) [+ SetParameters(corr_type, method)].Compute(x)
+        (sonar_autocorr) -> (correlations, lags, metrics dict)."""
+        x = _f64(x)
+        L = max(0, min(max_lag, len(x) - 1)) if len(x) else 0
+        corr, met = np.zeros(2 * L + 1), np.zeros(12)
+        self._check(self._L.sonar_autocorr(self._h, _ptr(x) if len(x) else None, len(x), max_lag,
+                                           _corr_enum(corr_type, CORR_TYPES), _corr_enum(method, CORR_METHODS),
+                                           _ptr(corr), _ptr(met), 0))
+        return corr, np.arange(-L, L + 1), _xcorr_metrics(met)
+
+    def xcorr_params_device(self, a_ptr, na, b_ptr, nb, max_lag, corr_type="pearson", method="time", use_fft=None,
+                            corr_ptr=None):
+        """xcorr_params on device memory (device_ptrs = 1): a, b and the optional correlation array
+        (2L + 1 doubles; None: library scratch) are device addresses -> metrics dict."""
+        t, m = _corr_enum(corr_type, CORR_TYPES), _corr_enum(method, CORR_METHODS)
+        if use_fft is None:
+            use_fft = m == CORR_METHODS["frequency"]
+        met = np.zeros(12)
+        self._check(self._L.sonar_xcorr_params(self._h, a_ptr, na, b_ptr, nb, max_lag, t, m, int(bool(use_fft)),
+                                               corr_ptr, _ptr(met), 1))
+        return _xcorr_metrics(met)
+
+    def autocorr_device(self, x_ptr, n, max_lag, corr_type="pearson", method="time", corr_ptr=None):
+        """autocorr on device memory (device_ptrs = 1) -> metrics dict."""
+        met = np.zeros(12)
+        self._check(self._L.sonar_autocorr(self._h, x_ptr, n, max_lag, _corr_enum(corr_type, CORR_TYPES),
+                                           _corr_enum(method, CORR_METHODS), corr_ptr, _ptr(met), 1))
+        return _xcorr_metrics(met)
 
     def dtw(self, q, r, band=-1, want_cost=False):
         q, r = _f64(q), _f64(r)
