@@ -2082,26 +2082,25 @@ size_t dtw_dn_bytes(const DtwGeom& g) {   // direction words + exit map + walk m
 size_t dtw_ck_bytes(const DtwGeom& g) { return (size_t)g.nb * (g.nr >= 64 ? g.nr / 64 : 1) * 64 * 8; }
 int64_t dtw_run_words(const DtwGeom& g) { return g.nb + (g.nr + 63) / 64 + 2; }
 size_t dtw_edge_bytes(const DtwGeom& g) { return (size_t)(g.nb > 1 ? g.nb - 1 : 1) * (g.nr + 1) * 8; }
+size_t dtw_codes_bytes(int64_t cap) { return (size_t)((cap + 1023) / 1024) * 64 * 4; }
+size_t dtw_path_bytes(int64_t cap) { return (size_t)cap * 16; }   // pc (8 B), pq and pr (4 B each) per point
+size_t dtw_wstart_bytes(int64_t P) { return (size_t)((P + 15) / 16 + 1) * sizeof(int2); }
 int64_t dtw_cn_index(const DtwGeom& g, int64_t i, int64_t j) {
   const int64_t b = (i - 1) >> 6, l = (i - 1) & 63, s = j - 1 + l;
   return ((b * ((g.S + 1) / 2) + (s >> 1)) << 7) + 2 * l + (s & 1);
 }
 
-int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, const DtwGeom& g, double* Cn,
-               uint32_t* Dn, uint64_t* E, int32_t* sync_words, uint32_t* codes, int64_t* plen, uint64_t* trace,
-               hipStream_t s, hipEvent_t mid, double* CK, int mode) {
-  // sync_words: [0] ticket, [1] error bits, [2] non-finite flag (set by the caller's probe), [3]
+int launch_dtw(DtwArgs a, bool fast, hipStream_t s, hipEvent_t mid) {
+  // a.sync: [0] ticket, [1] error bits, [2] non-finite flag (set by the caller's probe), [3]
   // unused, then the DTW_DIAG_WORDS-word diagnostic record at byte 16 (DTW_SYNC_BYTES in all)
-  if (hipMemsetAsync(sync_words, 0, 2 * sizeof(int32_t), s) != hipSuccess) return -5;
-  if (hipMemsetAsync(sync_words + 4, 0, DTW_DIAG_WORDS * 8, s) != hipSuccess) return -5;
-  if (g.nb > 1 && hipMemsetD32Async((hipDeviceptr_t)E, 0x7FF00001u, dtw_edge_bytes(g) / 4, s) != hipSuccess) return -5;
-  DtwArgs a{q, r, dim, band, g.nq, g.nr, g.nb, g.S, g.SW, Cn, Dn, reinterpret_cast<uint64_t*>(E), sync_words,
-            trace};
-  a.CK = CK;
-  a.diag = reinterpret_cast<uint64_t*>(sync_words + 4);
+  const DtwGeom g = dtw_geom(a);
+  const int dim = a.dim, band = a.band, mode = a.mode;   // the caller's band: a.band may change below
+  if (hipMemsetAsync(a.sync, 0, 2 * sizeof(int32_t), s) != hipSuccess) return -5;
+  if (hipMemsetAsync(a.sync + 4, 0, DTW_DIAG_WORDS * 8, s) != hipSuccess) return -5;
+  if (g.nb > 1 && hipMemsetD32Async((hipDeviceptr_t)a.E, 0x7FF00001u, dtw_edge_bytes(g) / 4, s) != hipSuccess) return -5;
+  a.diag = reinterpret_cast<uint64_t*>(a.sync + 4);
   a.dbg_stall = dtw_dbg_stall_band(false);
-  a.mode = mode;
-  if (!Cn && !CK) return -1;
+  if (!a.Cn && !a.CK) return -1;
   const DtwBatch nob{};
   const dim3 grid((unsigned)g.nb), block(64 * DTW_WAVES);
 #define SONAR_DTW_LAUNCH(DD)                                                                          \
@@ -2142,10 +2141,8 @@ int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, c
 #undef SONAR_DTW_LAUNCH
   if (mid) hipEventRecord(mid, s);
   if (dtw_serial_walk()) {
-    hipLaunchKernelGGL(dtw_walk_kernel, dim3(1), dim3(64), 0, s, Dn, g.nq, g.nr, g.SW, codes, plen);
+    hipLaunchKernelGGL(dtw_walk_kernel, dim3(1), dim3(64), 0, s, a.Dn, g.nq, g.nr, g.SW, a.codes, a.plen);
   } else {
-    a.codes = codes;
-    a.plen = plen;
     const DtwArgs* none = nullptr;
     hipLaunchKernelGGL(dtw_exit_map_kernel<false>, dim3((unsigned)dtw_nseg(g.nr), (unsigned)g.nb), dim3(64), 0, s, a,
                        none);
@@ -2163,20 +2160,19 @@ int launch_dtw_prepare(const double* x, int64_t n, int dim, int metric, double* 
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-int launch_dtw_path_cost(const double* Cn, const DtwGeom& g, const uint32_t* codes, int64_t P, int2* wstart,
-                         int32_t* pq, int32_t* pr, double* pc, hipStream_t s) {
+int launch_dtw_path_cost(const DtwArgs& a, int64_t P, hipStream_t s) {
   if (P <= 0) return 0;
   const int64_t nw = (P + 15) >> 4;
-  hipLaunchKernelGGL(dtw_path_scan_kernel<false>, dim3(1), dim3(1024), 0, s, codes, P, g.nq, g.nr, wstart,
+  hipLaunchKernelGGL(dtw_path_scan_kernel<false>, dim3(1), dim3(1024), 0, s, a.codes, P, a.nq, a.nr, a.wstart,
                      (const DtwArgs*)nullptr);
-  hipLaunchKernelGGL(dtw_path_points_kernel<false>, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, codes,
-                     (const int2*)wstart, P, Cn, g.S, pq, pr, pc, (const DtwArgs*)nullptr);
+  hipLaunchKernelGGL(dtw_path_points_kernel<false>, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, a.codes,
+                     a.wstart, P, a.Cn, a.S, a.pq, a.pr, a.pc, (const DtwArgs*)nullptr);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
 int launch_dtw_path_tiles(const DtwArgs& a, int64_t P, hipStream_t s) {
   if (P <= 0) return 0;
-  const DtwGeom g = dtw_geom(a.nq, a.nr);
+  const DtwGeom g = dtw_geom(a);
   if (hipMemsetAsync(a.runs, 0, 4, s) != hipSuccess) return -5;
   hipLaunchKernelGGL(dtw_path_runs_kernel<false>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, a,
                      (const DtwArgs*)nullptr);
@@ -2241,7 +2237,7 @@ int launch_dtw_batch(const DtwArgs* hargs, const DtwArgs* dargs, const int64_t* 
   if (!hargs[0].Cn) {   // CK mode (every DTW of a batch alike): the path-tile pass; runs zeroed by the caller
     int64_t max_tiles = 1;
     for (int k = 0; k < n; ++k) {
-      const int64_t t = dtw_run_words(dtw_geom(hargs[k].nq, hargs[k].nr)) - 2;
+      const int64_t t = dtw_run_words(dtw_geom(hargs[k])) - 2;
       max_tiles = t > max_tiles ? t : max_tiles;
     }
     hipLaunchKernelGGL(dtw_path_runs_kernel<true>, dim3((unsigned)((max_cap + 255) / 256), (unsigned)n), dim3(256), 0,

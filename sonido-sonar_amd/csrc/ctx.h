@@ -1,5 +1,5 @@
 // ctx.h -- internal state behind the opaque sonar_ctx / sonar_result handles,
-// shared by sonar_api.cpp (kernel-level entries) and go_api.cpp (Go-API mirror).
+// shared by the kernel-level entries (sonar_api.cpp, align_api.cpp, ...) and go_api.cpp (Go-API mirror).
 #pragma once
 #include "../../include/sonar_gpu.h"
 
@@ -7,6 +7,7 @@
 
 #include "kernels.h"
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <string>
@@ -134,23 +135,21 @@ void pinned_pool_trim();
 // chroma tables of frame size fs at sample rate sr, built once per context (sonar_api.cpp); null on
 // allocation failure
 const sonar_ctx::ChromaT* chroma_tables_for(sonar_ctx* c, int fs, int sr);
+// calculateActualMaxLag (correlation.go:452-461): the lags an NCC of na and nb samples computes
+inline int64_t ncc_max_lag(int64_t max_lag, int64_t na, int64_t nb) {
+  return std::max<int64_t>(std::min({max_lag, na - 1, nb - 1}), 0);
+}
 // NCC + chroma DTW of one stream pair with two stream synchronisations (align_impl's device
-// path, sonar_api.cpp): ncc_enqueue and dtw_enqueue only launch and queue their small results
+// path, align_api.cpp): ncc_enqueue and dtw_enqueue only launch and queue their small results
 // into pinned host memory; after one hipStreamSynchronize, ncc_metrics_host reads the
 // correlation and dtw_finish decodes the warping path into pinned host arrays (second sync).
 struct DtwPending {
-  const double *dq = nullptr, *dr = nullptr;
-  int64_t nq = 0, nr = 0;
-  int32_t dim = 0, band = -1;
+  sonar::DtwArgs a{};      // the queued DTW: its sequences, geometry and scratch (dtw_scratch)
   int64_t* st = nullptr;   // pinned: [0] path length, [1] sync words 0..1, [2] non-finite flag
 };
 int ncc_enqueue(sonar_ctx* c, const double* da, int64_t na, const double* db, int64_t nb, int32_t max_lag,
                 double** hcorr, int64_t* L);
 void ncc_metrics_host(const double* corr, int64_t L, int64_t na, int64_t nb, double* metrics);
-// the path-tile pass's arguments (launch_dtw_path_tiles) of one DTW in checkpoint mode
-sonar::DtwArgs tile_args(const double* q, const double* r, int dim, int band, const sonar::DtwGeom& g, uint64_t* E,
-                         double* CK, int32_t* runs, int32_t* pq, int32_t* pr, double* pc, int64_t* plen, double* cnm,
-                         int mode = 0 /* dtw_mode: step pattern and metric */);
 // the band kernel's status block of one DTW (int32 sync[4] + the DtwArgs::diag record): adds its
 // counters to c->dtw_ctr and, when the DTW timed out, returns the failure text with the record
 std::string dtw_status(sonar_ctx* c, const void* sync_block);

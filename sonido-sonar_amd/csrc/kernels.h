@@ -1,4 +1,4 @@
-// kernels.h -- launch interfaces between the C-ABI host layer (sonar_api.cpp)
+// kernels.h -- launch interfaces between the C-ABI host layer (*_api.cpp)
 // and the HIP kernels (*.hip).  Device pointers only; all launches are async
 // on the given stream.
 #pragma once
@@ -239,12 +239,18 @@ struct DtwGeom {
   int64_t nb;       // 64-row bands = ceil(nq / 64)
   int64_t S;        // sweep steps per band = nr + 63
   int64_t SW;       // 16-step direction words per band = ceil(S / 16)
+  int64_t cap() const { return nq + nr + 1; }   // room for the longest warping path (points)
 };
 DtwGeom dtw_geom(int64_t nq, int64_t nr);
 // bytes of the band-skewed cost store Cn, direction store Dn and edge buffer E
 size_t dtw_cn_bytes(const DtwGeom& g);
 size_t dtw_dn_bytes(const DtwGeom& g);
 size_t dtw_edge_bytes(const DtwGeom& g);
+// bytes of the walk's move codes and of a block of path costs + both index arrays, for cap path
+// points; of the decode's wstart scratch for a path of P points
+size_t dtw_codes_bytes(int64_t cap);
+size_t dtw_path_bytes(int64_t cap);
+size_t dtw_wstart_bytes(int64_t P);
 // offset (elements) of C[i][j] (1-based, i,j >= 1) inside Cn
 int64_t dtw_cn_index(const DtwGeom& g, int64_t i, int64_t j);
 // applyStepPattern's patterns (dtw.go:137-162) and GetDistanceFunction's metrics (distance.go:10-26;
@@ -258,19 +264,6 @@ inline int dtw_mode(int step, int metric) { return step | (metric << 8); }
 inline int dtw_row_len(int dim, int metric) { return metric >= DTW_METRIC_COSINE ? dim + 2 : dim; }
 // out[n][dim + 2] from x[n][dim]; every sum in Go's index order, unfused (distance.go:49-58, 82-102)
 int launch_dtw_prepare(const double* x, int64_t n, int dim, int metric, double* out, hipStream_t s);
-// forward sweep + backtrack; `fast` = every input finite (no NaN path in math.Min).  mode 0 runs the
-// Euclidean / symmetric2 instances; any other mode (dtw_mode) the band kernel's params family, with
-// q and r the prepared rows (dtw_row_len doubles each) for Cosine and Pearson
-int launch_dtw(const double* q, const double* r, int dim, int band, bool fast, const DtwGeom& g, double* Cn,
-               uint32_t* Dn, uint64_t* E, int32_t* sync_words /* [0] ticket, [1] error */,
-               uint32_t* codes /* walk moves, 2 bits each */, int64_t* plen,
-               uint64_t* trace /* nullable, [nb][8] diagnostics */, hipStream_t s,
-               hipEvent_t mid = nullptr /* recorded between the sweep and the walk */,
-               double* CK = nullptr /* Cn null: dtw_ck_bytes of checkpoint columns instead */, int mode = 0);
-// wstart: scratch of (P + 15) / 16 int2 (each code word's starting cell).  Cn null: only the
-// points (and the zero cost of border points) are written; launch_dtw_path_tiles adds the costs
-int launch_dtw_path_cost(const double* Cn, const DtwGeom& g, const uint32_t* codes, int64_t P, int2* wstart,
-                         int32_t* pq, int32_t* pr, double* pc, hipStream_t s);
 // costMatrix[1:] (nq x (nr+1), column 0 = +Inf) from the band-skewed store
 int launch_dtw_cost_rowmajor(const double* Cn, const DtwGeom& g, double* out, hipStream_t s);
 // One DTW's arguments (the band kernel's parameter; an array of them for launch_dtw_batch)
@@ -286,7 +279,7 @@ struct DtwArgs {
   uint64_t* trace; // optional [nb][8]: t_start, t_first_edge, t_end, sweep wait ticks (s_memrealtime, 100 MHz),
                    // the sweep's wait ticks on its distance waves and on the band above's edge,
                    // distance-wave-0 and code-wave wait ticks
-  // batched launches only (launch_dtw_batch): the walk / path-decode outputs of this DTW
+  // the walk / path-decode outputs of this DTW (wstart: dtw_wstart_bytes of scratch)
   uint32_t* codes;
   int64_t* plen;
   int2* wstart;
@@ -313,14 +306,16 @@ struct DtwArgs {
   //       without a new edge value), [14] those after which the next poll found new values,
   //  [15] waves of this DTW that timed out
   uint64_t* diag;
-  // tests only (SONAR_DTW_DBG_STALL=<band>): the sweep of that 64-row band stops after 1,024 steps
-  // without publishing more, so the
-  // pipeline's bounded waits and its diagnostic record can be exercised; -1: off
+  // tests only (SONAR_DTW_DBG_STALL=<band>): the sweep of that 64-row band stops after 1,024 steps without
+  // publishing more, so the pipeline's bounded waits and its diagnostic record can be exercised; -1: off
   int32_t dbg_stall = -1;
   // step pattern | metric << 8 (dtw_mode); 0 = symmetric2 / Euclidean, the only mode of the batched
   // launches.  Read by the band kernel's params family and the path-tile pass.
   int32_t mode = 0;
 };
+// the arguments of a DTW of geometry g, every pointer still null; and the geometry back
+inline DtwArgs dtw_args(const DtwGeom& g) { return {nullptr, nullptr, 0, 0, g.nq, g.nr, g.nb, g.S, g.SW}; }
+inline DtwGeom dtw_geom(const DtwArgs& a) { return {a.nq, a.nr, a.nb, a.S, a.SW}; }
 constexpr int DTW_DIAG_WORDS = 16;
 // bytes of a single DTW's sync block (launch_dtw): 4 status words + the diagnostic record
 constexpr int DTW_SYNC_BYTES = 16 + 8 * DTW_DIAG_WORDS;
@@ -330,6 +325,16 @@ enum DtwRole : int { DTW_ROLE_EDGE = 1, DTW_ROLE_FEEDER = 2, DTW_ROLE_SWEEP = 3,
 // the path-tile pass
 size_t dtw_ck_bytes(const DtwGeom& g);
 int64_t dtw_run_words(const DtwGeom& g);
+// forward sweep + backtrack of one DTW; `fast` = every input finite (no NaN path in math.Min).
+// a.mode 0 runs the Euclidean / symmetric2 instances; any other mode (dtw_mode) the band kernel's
+// params family, with q and r the prepared rows (dtw_row_len doubles each) for Cosine and Pearson.
+// Reads a.q, r, dim, band, the geometry, Cn or CK, Dn, E, sync (DTW_SYNC_BYTES), trace, codes, plen and
+// mode; zeroes the ticket, error and diagnostic words, fills E, sets diag and dbg_stall itself, and
+// records mid (nullable) between the sweep and the walk.
+int launch_dtw(DtwArgs a, bool fast, hipStream_t s, hipEvent_t mid = nullptr);
+// the P points of a walked DTW's path from a.codes into a.pq, pr, pc (scratch: a.wstart).  a.Cn null:
+// only the points (and the zero cost of border points) are written; launch_dtw_path_tiles adds the costs
+int launch_dtw_path_cost(const DtwArgs& a, int64_t P, hipStream_t s);
 // path costs and C[nq][nr] from CK + E (the band kernel's checkpoint columns and band edges), for
 // a path whose points (pq, pr) are already written: one wave per 64 x 64 tile the path visits
 // recomputes the tile's cells in the band kernel's arithmetic (bit-identical).  Needs a.q, r, dim,

@@ -111,19 +111,36 @@ int elt_size(int32_t dtype) { return dtype == SONAR_F32 ? 4 : 8; }
 
 size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// where a pair's regions start in the batch's buffers ("pb.chroma", "pb.CK", ...; correlations and
+// paths inside "pb.small"); as a batch's running totals, the bytes of those buffers so far
+struct PairRegions { size_t chroma = 0, ck = 0, runs = 0, dn = 0, e = 0, codes = 0, wst = 0, path = 0, corr = 0; };
 struct PairGeo {
-  int64_t k = 0, nq = 0, nr = 0, Fq = 0, Fr = 0, Eq = 0, Er = 0, L = 0, mlf = 0, cap = 0;
+  int64_t k = 0, nq = 0, nr = 0, Fq = 0, Fr = 0, Eq = 0, Er = 0, L = 0, mlf = 0;
   bool corr = false;
   sonar::DtwGeom g{};
-  size_t chroma = 0, ck = 0, runs = 0, dn = 0, e = 0, codes = 0, wst = 0, path = 0, corr_off = 0;   // region offsets
+  PairRegions at;
 };
 
-// device bytes one pair of a batch holds (chroma, the DTW stores, the path)
-size_t pair_bytes(const PairGeo& p) {
-  return al256((size_t)(p.Fq + p.Fr) * 96) +
-         al256(sonar::dtw_ck_bytes(p.g)) + al256((size_t)sonar::dtw_run_words(p.g) * 4) + al256(sonar::dtw_dn_bytes(p.g)) +
-         al256(sonar::dtw_edge_bytes(p.g)) + al256((size_t)((p.cap + 1023) / 1024) * 256) +
-         al256((size_t)((p.cap + 15) / 16 + 1) * 8) + al256((size_t)p.cap * 16) + al256((size_t)(2 * p.L + 1) * 8) +
+// The device layout of one pair of a batch (chroma, the DTW stores, the path, the correlation):
+// places p's regions at the running totals and advances them, every region 256-byte aligned
+void place_pair(PairGeo& p, PairRegions& t) {
+  auto take = [](size_t& total, size_t bytes) { const size_t off = total; total += al256(bytes); return off; };
+  p.at.chroma = take(t.chroma, (size_t)(p.Fq + p.Fr) * 96);
+  p.at.ck = take(t.ck, sonar::dtw_ck_bytes(p.g));
+  p.at.runs = take(t.runs, (size_t)sonar::dtw_run_words(p.g) * 4);
+  p.at.dn = take(t.dn, sonar::dtw_dn_bytes(p.g));
+  p.at.e = take(t.e, sonar::dtw_edge_bytes(p.g));
+  p.at.codes = take(t.codes, sonar::dtw_codes_bytes(p.g.cap()));
+  p.at.wst = take(t.wst, sonar::dtw_wstart_bytes(p.g.cap()));
+  p.at.path = take(t.path, sonar::dtw_path_bytes(p.g.cap()));
+  p.at.corr = take(t.corr, (size_t)(2 * p.L + 1) * 8);
+}
+
+// device bytes one pair of a batch holds: its regions, placed alone
+size_t pair_bytes(PairGeo p) {
+  PairRegions t;
+  place_pair(p, t);
+  return t.chroma + t.ck + t.runs + t.dn + t.e + t.codes + t.wst + t.path + t.corr +
          // batched features (feat_batch): pre-emphasised signals, DC scratch, energies, NCC inputs
          al256((size_t)p.nq * 8) + al256((size_t)p.nr * 8) + al256(sonar::dc_preemph_scratch_bytes(p.nq)) +
          al256(sonar::dc_preemph_scratch_bytes(p.nr)) + 2 * al256((size_t)(p.Eq + p.Er + 2) * 8) + 256;
@@ -199,7 +216,7 @@ bool feat_batch(sonar_ctx* w, const std::vector<PairGeo>& pg, int32_t sr, int32_
       j.Fe = side ? p.Er : p.Eq;
       j.energy = (double*)(en + eo); eo += al256((size_t)std::max<int64_t>(j.Fe, 1) * 8);
       j.F = side ? p.Fr : p.Fq;
-      j.chroma = (double*)(chroma + p.chroma) + (side ? p.Fq * 12 : 0);
+      j.chroma = (double*)(chroma + p.at.chroma) + (side ? p.Fq * 12 : 0);
       e2[side] = j.energy;
     }
     if (p.corr) {
@@ -209,7 +226,7 @@ bool feat_batch(sonar_ctx* w, const std::vector<PairGeo>& pg, int32_t sr, int32_
       j.xb = j.xa + p.Eq;
       j.stats = (double*)(nx + xo + al256((size_t)(p.Eq + p.Er) * 8));
       xo += al256((size_t)(p.Eq + p.Er) * 8) + 256;
-      j.corr = (double*)(corr + p.corr_off);
+      j.corr = (double*)(corr + p.at.corr);
     }
   }
   (void)sw;
@@ -237,21 +254,13 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
   HIP_TRY(w, hipSetDevice(w->device));
   hipStream_t s = w->stream;
   std::vector<PairGeo> pg = in;
-  size_t chroma_b = 0, ck_b = 0, runs_b = 0, dn_b = 0, e_b = 0, codes_b = 0, wst_b = 0, path_b = 0, corr_b = 0;
+  PairRegions tot;
   int64_t maxE = 1, maxn = 1, max_cap = 1, total_bands = 0, maxnb = 0;
   for (auto& p : pg) {
-    p.chroma = chroma_b; chroma_b += al256((size_t)(p.Fq + p.Fr) * 96);
-    p.ck = ck_b; ck_b += al256(sonar::dtw_ck_bytes(p.g));
-    p.runs = runs_b; runs_b += al256((size_t)sonar::dtw_run_words(p.g) * 4);
-    p.dn = dn_b; dn_b += al256(sonar::dtw_dn_bytes(p.g));
-    p.e = e_b; e_b += al256(sonar::dtw_edge_bytes(p.g));
-    p.codes = codes_b; codes_b += al256((size_t)((p.cap + 1023) / 1024) * 256);
-    p.wst = wst_b; wst_b += al256((size_t)((p.cap + 15) / 16 + 1) * 8);
-    p.path = path_b; path_b += al256((size_t)p.cap * 16);
-    p.corr_off = corr_b; corr_b += al256((size_t)(2 * p.L + 1) * 8);
+    place_pair(p, tot);
     maxE = std::max({maxE, p.Eq, p.Er});
     maxn = std::max({maxn, p.nq, p.nr});
-    max_cap = std::max(max_cap, p.cap);
+    max_cap = std::max(max_cap, p.g.cap());
     maxnb = std::max(maxnb, p.g.nb);
     total_bands += p.g.nb;   // band-kernel tickets
   }
@@ -263,13 +272,13 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
                cs_b = al256((size_t)n * sizeof(sonar::host::CorrSums)),
                args_b = al256((size_t)n * sizeof(sonar::DtwArgs)), start_b = al256((size_t)(n + 1) * 8),
                map_b = al256((size_t)total_bands * 8), sj_b = al256((size_t)n * sizeof(sonar::ScoreJob));
-  char* chroma = (char*)dbuf(w, "pb.chroma", chroma_b);
-  char* CK = (char*)dbuf(w, "pb.CK", ck_b);
-  char* runs = (char*)dbuf(w, "pb.runs", runs_b);
-  char* Dn = (char*)dbuf(w, "pb.Dn", dn_b);
-  char* E = (char*)dbuf(w, "pb.E", e_b);
-  char* codes = (char*)dbuf(w, "pb.codes", codes_b);
-  char* wst = (char*)dbuf(w, "pb.wstart", wst_b);
+  char* chroma = (char*)dbuf(w, "pb.chroma", tot.chroma);
+  char* CK = (char*)dbuf(w, "pb.CK", tot.ck);
+  char* runs = (char*)dbuf(w, "pb.runs", tot.runs);
+  char* Dn = (char*)dbuf(w, "pb.Dn", tot.dn);
+  char* E = (char*)dbuf(w, "pb.E", tot.e);
+  char* codes = (char*)dbuf(w, "pb.codes", tot.codes);
+  char* wst = (char*)dbuf(w, "pb.wstart", tot.wst);
   // small holds, in the pinned host buffer's layout: status words + ticket, diagnostic records, the
   // scorer reductions (PathSums, CorrSums), then DTW arguments, ticket starts, band-major map and
   // score jobs (one upload), correlations, paths -- so the batch's results come back in ONE copy of
@@ -278,10 +287,10 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
   // tests) copies correlations and paths back instead and runs them on the host, as a
   // SONAR_PAIR_DUMP does.
   const size_t head_b = stat_b + diag_b + ps_b + cs_b, up_b = args_b + start_b + map_b + sj_b;
-  const size_t small_b = head_b + up_b + corr_b + path_b;
+  const size_t small_b = head_b + up_b + tot.corr + tot.path;
   char* small = (char*)dbuf(w, "pb.small", small_b);
   char* corr = small ? small + (head_b + up_b) : nullptr;
-  char* path = small ? corr + corr_b : nullptr;
+  char* path = small ? corr + tot.corr : nullptr;
   // SONAR_DTW_TRACE=<file> (diagnostics): every band's sweep timestamps (dtw_band_kernel's trace
   // words) appended to <file> as {pair, band, 8 trace words} records
   const char* trace_path = std::getenv("SONAR_DTW_TRACE");
@@ -322,7 +331,7 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
   auto* hsj = (sonar::ScoreJob*)(h + ab + args_b + start_b + map_b);
   auto* dsj = (const sonar::ScoreJob*)(small + ab + args_b + start_b + map_b);
   char* hcorr = h + head_b + up_b;
-  char* hpath = hcorr + corr_b;
+  char* hpath = hcorr + tot.corr;
   const char* dump_dir = std::getenv("SONAR_PAIR_DUMP");
   const char* hs_env = std::getenv("SONAR_PAIR_HOST_SCORES");
   const bool host_scores = dump_dir || (hs_env && std::atoi(hs_env) != 0);
@@ -336,7 +345,7 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
   for (int i = 0; i < n; ++i) {
     const PairGeo& p = pg[i];
     const double *dq = q_pcm[p.k], *dr = r_pcm[p.k];
-    double* cq = (double*)(chroma + p.chroma);
+    double* cq = (double*)(chroma + p.at.chroma);
     double* cr = cq + p.Fq * 12;
     if (!fb) {
       if (!device_ptrs) {
@@ -347,23 +356,22 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
       int rc = sonar_music_alignment_features(w, dq, p.nq, sr, sw, hop, fw, hop, eq, cq, 1);
       if (rc == SONAR_OK) rc = sonar_music_alignment_features(w, dr, p.nr, sr, sw, hop, fw, hop, er, cr, 1);
       if (rc != SONAR_OK) return rc;
-      if (p.corr && sonar::launch_ncc(eq, p.Eq, er, p.Er, p.L, xa, xb, st, (double*)(corr + p.corr_off), s) != 0)
+      if (p.corr && sonar::launch_ncc(eq, p.Eq, er, p.Er, p.L, xa, xb, st, (double*)(corr + p.at.corr), s) != 0)
         return fail(w, SONAR_ERR_DEVICE, "ncc launch failed");
     }
     int32_t* sync = dstat + 8 * i + 4;
     sonar::DtwArgs& a = hargs[i];
-    a = sonar::DtwArgs{};
+    a = sonar::dtw_args(p.g);
     a.q = cq; a.r = cr; a.dim = 12; a.band = -1;
-    a.nq = p.g.nq; a.nr = p.g.nr; a.nb = p.g.nb; a.S = p.g.S; a.SW = p.g.SW;
-    a.Cn = nullptr; a.CK = (double*)(CK + p.ck); a.runs = (int32_t*)(runs + p.runs); a.Dn = (uint32_t*)(Dn + p.dn); a.E = (uint64_t*)(E + p.e); a.sync = sync;
-    a.codes = (uint32_t*)(codes + p.codes); a.plen = (int64_t*)(dstat + 8 * i); a.wstart = (int2*)(wst + p.wst);
-    a.pc = (double*)(path + p.path); a.pq = (int32_t*)(a.pc + p.cap); a.pr = a.pq + p.cap;
+    a.Cn = nullptr; a.CK = (double*)(CK + p.at.ck); a.runs = (int32_t*)(runs + p.at.runs); a.Dn = (uint32_t*)(Dn + p.at.dn); a.E = (uint64_t*)(E + p.at.e); a.sync = sync;
+    a.codes = (uint32_t*)(codes + p.at.codes); a.plen = (int64_t*)(dstat + 8 * i); a.wstart = (int2*)(wst + p.at.wst);
+    a.pc = (double*)(path + p.at.path); a.pq = (int32_t*)(a.pc + p.g.cap()); a.pr = a.pq + p.g.cap();
     a.cnm = (double*)(dstat + 8 * i + 2);
     a.diag = ddiag + (size_t)i * sonar::DTW_DIAG_WORDS;
     a.trace = trb ? (uint64_t*)(trb + (size_t)acc * 64) : nullptr;
     a.dbg_stall = sonar::dtw_dbg_stall_band(true);
     sonar::ScoreJob& sj = hsj[i];
-    sj = sonar::ScoreJob{a.pq, a.pr, a.pc, a.plen, p.corr ? (const double*)(corr + p.corr_off) : nullptr,
+    sj = sonar::ScoreJob{a.pq, a.pr, a.pc, a.plen, p.corr ? (const double*)(corr + p.at.corr) : nullptr,
                          2 * p.L + 1, dps + i, dcs + i};
     hstart[i] = acc;
     acc += p.g.nb;
@@ -435,28 +443,28 @@ int align_batch(sonar_ctx* w, const std::vector<PairGeo>& in, const double* cons
     if (dump_dir) {
       // tests only: the batched DTW's raw outputs of pair k (path length, C[nq][nr], path costs,
       // query and reference indices) into <dump>/pair_<k>.bin, to be checked against the oracle
-      const double* pc = (const double*)(hpath + p.path);
+      const double* pc = (const double*)(hpath + p.at.path);
       const std::string fn = std::string(dump_dir) + "/pair_" + std::to_string(p.k) + ".bin";
       if (FILE* f = std::fopen(fn.c_str(), "wb")) {
         std::fwrite(&P, 8, 1, f);
         std::fwrite(&cnm, 8, 1, f);
         std::fwrite(pc, 8, (size_t)P, f);
-        std::fwrite(pc + p.cap, 4, (size_t)P, f);
-        std::fwrite((const int32_t*)(pc + p.cap) + p.cap, 4, (size_t)P, f);
+        std::fwrite(pc + p.g.cap(), 4, (size_t)P, f);
+        std::fwrite((const int32_t*)(pc + p.g.cap()) + p.g.cap(), 4, (size_t)P, f);
         std::fclose(f);
       }
     }
     sonar::detail::AlignIn ai;
     ai.q_pcm_len = p.nq; ai.r_pcm_len = p.nr; ai.sample_rate = sr; ai.hop = hop;
     if (p.corr) {
-      if (host_scores) ai.corr = (const double*)(hcorr + p.corr_off);
+      if (host_scores) ai.corr = (const double*)(hcorr + p.at.corr);
       else ai.corr_sums = hcs + i;
       ai.L = p.L; ai.nqe = p.Eq; ai.nre = p.Er; ai.mlf = p.mlf;
     }
     ai.has_dtw = true;
     if (host_scores) {
-      const double* pc = (const double*)(hpath + p.path);
-      ai.pc = pc; ai.pq = (const int32_t*)(pc + p.cap); ai.pr = ai.pq + p.cap;
+      const double* pc = (const double*)(hpath + p.at.path);
+      ai.pc = pc; ai.pq = (const int32_t*)(pc + p.g.cap()); ai.pr = ai.pq + p.g.cap();
     } else {
       ai.path_sums = hps + i;
     }
@@ -545,7 +553,6 @@ int sonar_align_pairs(sonar_ctx* c, int64_t npairs, const double* const* q_pcm, 
       p.L = std::max<int64_t>(0, std::min({p.mlf, p.Eq - 1, p.Er - 1}));
     }
     p.g = sonar::dtw_geom(p.Fq, p.Fr);
-    p.cap = p.Fq + p.Fr + 1;
     geo.push_back(p);
   }
   std::vector<std::vector<PairGeo>> batches;

@@ -70,11 +70,7 @@ int xcorr_run(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_
                                                 std::to_string(sonar::XCORR_FFT_MAX_N) + " points");
     N = next_pow2(na + nb - 1);
   }
-  int64_t L = max_lag;                                            // calculateActualMaxLag :452-461
-  L = std::min<int64_t>(L, na - 1);
-  L = std::min<int64_t>(L, nb - 1);
-  L = std::max<int64_t>(L, 0);
-  const int64_t nl = 2 * L + 1;
+  const int64_t L = sonar::detail::ncc_max_lag(max_lag, na, nb), nl = 2 * L + 1;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const double *da = a, *db = b;
@@ -122,11 +118,9 @@ int xcorr_run(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_
   HIP_TRY(c, hipStreamSynchronize(s));
   if (corr && !device_ptrs) std::memcpy(corr, hc.data(), nl * 8);
   if (metrics) {
-    const auto m = sonar::host::ncc_metrics(hc.data(), nl, L, na, nb);
-    const double v[12] = {m.peak_corr, (double)m.peak_lag, (double)m.peak_index, m.p_value, m.snr, m.sharpness,
-                          m.second_peak, m.psl, (double)m.overlap, (double)m.num_lags, (double)method,
-                          (double)corr_type};
-    std::memcpy(metrics, v, sizeof(v));
+    sonar::detail::ncc_metrics_host(hc.data(), L, na, nb, metrics);   // [0..9], as sonar_ncc
+    metrics[10] = (double)method;
+    metrics[11] = (double)corr_type;
   }
   return SONAR_OK;
 }
