@@ -23,7 +23,8 @@
 //    v_permlane16_swap (bit 4) and a DPP row_ror:8 exchange (bit 3) -- no LDS.
 //    Lane b0 + 8 (k1 & 7) then holds b1 (and k1 >> 3) in registers: pass 2 =
 //    two DFT8 over b1, twiddle w_64^{b0 c0}.
-//  * T2: one LDS transpose (b64, lane stride 136 B: conflict-free reads) to the
+//  * T2: one LDS transpose (b64; rows by b0, columns by reader lane: conflict-free both ways,
+//    one store sequence for all 64 lanes) to the
 //    "combo" layout: lane L holds the combos (k1, c0) with residues r and 128 - r
 //    (r = k1 + 16 c0), 8 values b0 each; pass 3 = two DFT8 over b0 gives
 //    Z[r + 128 c1] and Z[128 - r + 128 c1], so Z_k and Z_{1024-k} meet in one lane.
@@ -226,12 +227,32 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// T2 destination byte offsets (float32 layout: complex units x 8) for lanes with k1 & 7 == 0:
-// [h][c0] -> L3 * 136 + slot * 64 (see comboLane in DESIGN.md / the header comment); scaled by the
-// complex size for float64
-constexpr int kT2Irreg[2][8] = {
-    {63 * 136, 60 * 136, 61 * 136, 62 * 136, 63 * 136 + 64, 62 * 136 + 64, 61 * 136 + 64, 60 * 136 + 64},
-    {56 * 136, 57 * 136, 58 * 136, 59 * 136, 59 * 136 + 64, 58 * 136 + 64, 57 * 136 + 64, 56 * 136 + 64}};
+// T2 buffer, "b0-major": the 8-vector (over b0) of residue r is 8 complex RS apart, element b0 at
+// complex index RS b0 + u, u = t2_col(L) for slot A of reader lane L and t2_col(L) + 64 for slot B.
+//  * reader lane L = 8 a + c keeps the residues it always had (rA / rB below); its column is
+//    2 P + ((a & 1) ^ 1) + 16 (a >> 1), P = pi(c) = (0,1,2,3,4,7,6,5) for a < 7 and (1,2,3,0,5,6,7,4) for
+//    the eight lanes 56..63 that hold the residues of k1 = 0 and 8.  A half-wave's 32 columns are
+//    distinct mod 32 (ds_read_b64), 16 consecutive lanes' (ds_read2*_b64) and a ds_read_b128 group's
+//    16 distinct mod 16: conflict-free loads.
+//  * a column's parity is its residue's, so the two k1 of a 16-lane store group (k1 and k1 + 1) land
+//    on columns of opposite parity, and with RS = 2 mod 16 the 16 lanes' 2 b0 + u cover all 32 banks
+//    (float32, ds_write_b64); float64 stores (ds_write_b128, 8 lanes of one k1) need RS odd.
+//  * every lane runs the same 16 stores: address = one of five per-lane bases + an immediate
+//    2 pi(c) (h = 0) or 2 pi(7 - c) (h = 1).  Lanes with k1 & 7 != 0 hold two distinct values in the
+//    five (one per h); the k1 & 7 == 0 lanes need all five (kT2Irr): pi closes the k1 = 0 group and
+//    the low half of k1 = 8 with one base each, the high half of k1 = 8 needs two.
+// tools/pair_model.py is the specification of this layout (tests/test_pair_layout_cpu.py).
+template <typename T> constexpr int t2_rs() { return sizeof(T) == 8 ? 129 : 130; }
+__host__ __device__ constexpr int t2_pi(int c) { return c < 5 ? c : 12 - c; }
+__host__ __device__ constexpr int t2_q(int a) { return ((a & 1) ^ 1) + 16 * (a >> 1); }
+__device__ __forceinline__ int t2_col(int lane) {
+  const int a = lane >> 3, c = lane & 7;
+  const int x = (c & 4) | ((c + 1) & 3);
+  return 2 * (a < 7 ? t2_pi(c) : x) + t2_q(a);
+}
+// store base of instruction (h, c): h = 0: c < 4 -> 0, else 1; h = 1: c < 4 -> 2, c == 4 -> 3, else 4
+__host__ __device__ constexpr int t2_reg(int h, int c) { return h == 0 ? (c >= 4) : (c < 4 ? 2 : (c == 4 ? 3 : 4)); }
+constexpr int kT2Irr[5] = {56, 112, 40, 106, 114};   // the five bases of the k1 & 7 == 0 lanes (complex columns)
 
 // power rows [bin][2 frames]: bin k at row k + PAD (k >> 4) -- pad rows after every 16 bins make the
 // split's stores (bins k1 + 16 c0 across a lane group) conflict-free: two for the float32 kernel's
@@ -243,7 +264,10 @@ constexpr int kPRows = 600;
 // one wave's LDS region for arithmetic type T (bytes)
 template <typename T> struct Lay {
   static constexpr int ES = (int)sizeof(T), CB = 2 * ES;       // element, complex
-  static constexpr int T2Stride = 17 * CB;                     // bytes per lane row of the T2 buffer (17 complex)
+  static constexpr int T2Stride = 17 * CB;                     // the region holds 64 x 17 complex: the T2 buffer
+                                                               // (8 rows of t2_rs complex) fits inside it
+  static constexpr int RS = t2_rs<T>() * CB;                   // bytes per b0 row of the T2 buffer
+  static_assert(8 * RS <= 64 * T2Stride, "T2 buffer");
   static constexpr int WaveBytes = 64 * T2Stride + 16;         // + a complex that stays zero (unused filter sources)
   static constexpr int PB = 2 * ES;                            // power row: [2 frames]
   static constexpr int PadR = mfcc_pair_pad_rows(ES == 8);     // pad rows per 16 power rows
@@ -320,8 +344,8 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
   if (threadIdx.x == 0) *s_next = 0;
   unsigned char* wb = smem + p.lds_wave0 + wave * L::WaveBytes;
   // Zero the wave's region once: the filterbank chunks read up to 11 rows past bin 512 with
-  // zero weight, and some of those bytes (the unused 17th complex of T2 lane rows 33/34) are
-  // never written by this kernel -- stale LDS from an earlier launch can hold NaN/Inf, and
+  // zero weight, and some bytes of the region (the two pad complex of a T2 row, the tail past the
+  // T2 rows) are never written by this kernel -- stale LDS from an earlier launch can hold NaN/Inf, and
   // 0 * NaN would turn the last filter into ln(1e-10) (seen in tools/pair_stress2.py).
   for (int i = lane; i < L::WaveBytes / 16; i += 64)
     *reinterpret_cast<float4*>(wb + 16 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -359,9 +383,13 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
   }
   // lane masks for the bit-3 exchange: m_hi3 = lanes with bit 3 set, m_lo3 = the rest
   const uint64_t m_hi3 = 0xff00ff00ff00ff00ull, m_lo3 = ~m_hi3;
-  // T2 write bases (regular lanes, kl != 0): h = 0 -> + stride c0, h = 1 -> + stride (7 - c0)
-  const int t2b0 = (kl - 1) * 8 * L::T2Stride + L::CB * b0;
-  const int t2b1 = (7 - kl) * 8 * L::T2Stride + 8 * L::CB + L::CB * b0;
+  // T2 store bases (bytes): lanes with kl != 0 write slot A of reader lanes 8 (kl - 1) + c (h = 0) and
+  // slot B of 8 (7 - kl) + 7 - c (h = 1); the kl == 0 lanes' five differ (kT2Irr)
+  int t2b[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++)
+    t2b[i] = L::RS * b0 + L::CB * (kl != 0 ? (i < 2 ? t2_q(kl - 1) : 64 + t2_q(7 - kl)) : kT2Irr[i]);
+  const int t2r = L::CB * t2_col(lane);                         // this lane's column as T2 reader
   // combo residues of this lane (as T2 reader / split)
   int rA;
   if (lane < 56) rA = (lane >> 3) + 1 + 16 * (lane & 7);
@@ -556,22 +584,17 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
       v[c] = cmul(v[c], w); v[8 + c] = cmul(v[8 + c], w);
     }
     // ---- T2: LDS transpose into the combo layout ---------------------------------
-    if (kl != 0) {
 #pragma unroll
-      for (int c = 0; c < 8; c++) {
-        st2<T>(wb + t2b0 + L::T2Stride * c, v[c].x, v[c].y);
-        st2<T>(wb + t2b1 + L::T2Stride * (7 - c), v[8 + c].x, v[8 + c].y);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        st2<T>(wb + L::CB * b0 + kT2Irreg[0][c] * (L::CB / 8), v[c].x, v[c].y);
-        st2<T>(wb + L::CB * b0 + kT2Irreg[1][c] * (L::CB / 8), v[8 + c].x, v[8 + c].y);
-      }
+    for (int c = 0; c < 8; c++) {
+      st2<T>(wb + t2b[t2_reg(0, c)] + 2 * L::CB * t2_pi(c), v[c].x, v[c].y);
+      st2<T>(wb + t2b[t2_reg(1, c)] + 2 * L::CB * t2_pi(7 - c), v[8 + c].x, v[8 + c].y);
     }
     wave_lds_sync();
 #pragma unroll
-    for (int j = 0; j < 16; j++) v[j] = ld2<T>(wb + lane * L::T2Stride + L::CB * j);
+    for (int j = 0; j < 8; j++) {
+      v[j] = ld2<T>(wb + t2r + L::RS * j);
+      v[8 + j] = ld2<T>(wb + t2r + 64 * L::CB + L::RS * j);
+    }
     wave_lds_sync();
     if (HL_PHASE_PRIO) __builtin_amdgcn_s_setprio(1);
     // ---- pass 3: DFT8 over b0 for both combos --------------------------------------
@@ -579,9 +602,13 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
     dft8<8, 1>(v);    // B[c1] = Z[rB + 128 c1]
     // ---- power spectra of both frames: P_t = |Za + conj Zb|^2, P_t+1 = |Za - conj Zb|^2
     //      (the 1/4 is folded into the filterbank weights)
-    auto pw = [&](C a, C b, int off) {
+    //      The sums of squares are explicit FMAs: which square is the fused one decides the last bit,
+    //      and left to the compiler's contraction that choice moved with unrelated code (the T2 layout).
+    //      YF (the imaginary parts' squares fused) is the order the c = 1 bins have always had.
+    auto pw = [&](C a, C b, int off, bool yf = false) {
       const T sr = a.x + b.x, si = a.y - b.y, dr = a.x - b.x, di = a.y + b.y;
-      T p0 = sr * sr + si * si, p1 = dr * dr + di * di;
+      T p0 = yf ? fma_(si, si, sr * sr) : fma_(sr, sr, si * si);
+      T p1 = yf ? fma_(di, di, dr * dr) : fma_(dr, dr, di * di);
       if (POW2) { p0 *= p0; p1 *= p1; }
       st2<T>(wb + off, p0, p1);
     };
@@ -589,7 +616,7 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       const C sec = self ? v[(8 - c) & 7] : v[15 - c];         // B[7 - c], or A[(8 - c) & 7] on lane 63
-      pw(v[c], sec, pA + R128 * c);
+      pw(v[c], sec, pA + R128 * c, c == 1);
     }
     pw(self ? v[12] : v[4], v[11], pB + 3 * R128);             // (A4, B3) / lane 63: (B4, B3)
 #pragma unroll

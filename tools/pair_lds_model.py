@@ -19,6 +19,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pair_model as PM  # noqa: E402  (the T2 layout's specification)
 
 
 def _oracle():
@@ -162,10 +164,6 @@ def tables(sr, nf, W=1024, order_kind="b64", pad=2):
                 MS=max(len(s) for s in src))
 
 
-T2_IRREG = [[63 * 136, 60 * 136, 61 * 136, 62 * 136, 63 * 136 + 64, 62 * 136 + 64, 61 * 136 + 64, 60 * 136 + 64],
-            [56 * 136, 57 * 136, 58 * 136, 59 * 136, 59 * 136 + 64, 58 * 136 + 64, 57 * 136 + 64, 56 * 136 + 64]]
-
-
 def model(t, f64, tw2_row=8, dct_pad=4, pad=2, planes=False):
     ES = 8 if f64 else 4
     CB, T2S, PB = 2 * ES, 34 * ES, 2 * ES
@@ -182,22 +180,19 @@ def model(t, f64, tw2_row=8, dct_pad=4, pad=2, planes=False):
     def add(name, kind, addr):
         ph[name] = ph.get(name, 0) + extra(kind, addr)
 
-    # T2 transpose: regular lanes (kl != 0) and the irregular lanes 0-7 as two instruction streams
+    # T2 transpose: 16 stores, the same instructions for all 64 lanes (pair_model: b0-major rows,
+    # columns by reader lane); loads of slot A / slot B, priced as single reads and, for float32, also
+    # under the ds_read2*_b64 rule the compiler's pairing of them falls under
+    base = PM.store_bases(f64)
     for c in range(8):
         for h in range(2):
-            a = [None] * 64
-            b = [None] * 64
-            for l in range(64):
-                b0, kl = l & 7, l >> 3
-                if kl:
-                    a[l] = ((kl - 1) * 8 * T2S + CB * b0 + T2S * c) if h == 0 else \
-                        ((7 - kl) * 8 * T2S + 8 * CB + CB * b0 + T2S * (7 - c))
-                else:
-                    b[l] = CB * b0 + T2_IRREG[h][c] * (CB // 8)
-            add("t2_store", wr2, a)
-            add("t2_store", wr2, b)
+            add("t2_store", wr2, [CB * int(base[l, PM.store_reg(h, c)] + PM.store_imm(h, c)) for l in range(64)])
+    RS = PM.row_stride(f64)
     for j in range(16):
-        add("t2_load", rd2, [l * T2S + CB * j for l in range(64)])
+        a = [CB * (PM.col(l) + 64 * (j >> 3) + RS * (j & 7)) for l in range(64)]
+        add("t2_load", rd2, a)
+        if not f64:
+            ph["t2_load"] += extra("_r2", a)
     # power rows
     rA = []
     for l in range(64):

@@ -2,17 +2,69 @@
 
 Emulates 64 lanes x 16 complex registers through pass 1, T1 (permlane32/16 swaps,
 row_ror:8 exchange), pass 2, T2 (LDS combo layout), pass 3 and the pair split, and
-checks the per-bin power of both frames against numpy.fft.rfft."""
+checks the per-bin power of both frames against numpy.fft.rfft.
+
+This file is the specification of the T2 layout (tests/test_pair_layout_cpu.py holds the kernel's
+constants to it; tools/pair_lds_model.py prices its bank conflicts):
+  * the T2 buffer is "b0-major": element b0 of a residue's 8-vector sits at complex index
+    RS b0 + column, RS = row_stride(f64); reader lane L's slot A is column col(L), slot B col(L) + 64;
+  * every lane runs the same 16 stores, instruction (h, c) storing register 8 h + c at
+    base[store_reg(h, c)] + store_imm(h, c); store_bases() gives each lane's five bases.
+Lanes with k1 & 7 == 0 (lanes 0-7) differ from the others only in the values of their bases."""
 import numpy as np
 
 L = np.arange(64)
+PI = (0, 1, 2, 3, 4, 7, 6, 5)          # column order of the eight c0 of a k1 group
+XI = (1, 2, 3, 0, 5, 6, 7, 4)          # the same for reader lanes 56..63 (residues of k1 = 0 and 8)
+IRR = (56, 112, 40, 106, 114)          # the five store bases (columns) of the lanes with k1 & 7 == 0
+
+
+def row_stride(f64=False):
+    """complex per b0 row: = 2 mod 16 for the float32 ds_write_b64 groups, odd for float64's b128"""
+    return 129 if f64 else 130
+
+
+def q_of(a):
+    return ((a & 1) ^ 1) + 16 * (a >> 1)
+
+
+def col(lane):
+    """column of reader lane `lane` (slot A; slot B is 64 further)"""
+    a, c = lane >> 3, lane & 7
+    return 2 * (PI[c] if a < 7 else XI[c]) + q_of(a)
+
+
+def store_reg(h, c):
+    return (1 if c >= 4 else 0) if h == 0 else (2 if c < 4 else 3 if c == 4 else 4)
+
+
+def store_imm(h, c):
+    """lane-uniform immediate (complex units) of store instruction (h, c)"""
+    return 2 * PI[c] if h == 0 else 2 * PI[7 - c]
+
+
+def store_bases(f64=False):
+    """[lane][reg] -> complex index"""
+    out = np.empty((64, 5), int)
+    for lane in range(64):
+        b0, kl = lane & 7, lane >> 3
+        for i in range(5):
+            u = IRR[i] if kl == 0 else (q_of(kl - 1) if i < 2 else 64 + q_of(7 - kl))
+            out[lane, i] = row_stride(f64) * b0 + u
+    return out
+
+
+def residues():
+    """(rA, rB) of the 64 reader lanes; lane 63 holds the self-paired residues 0 and 64"""
+    rA = np.where(L < 56, (L >> 3) + 1 + 16 * (L & 7), np.where(L < 60, 8 + 16 * (L - 56), np.where(L < 63, 16 * (L - 59), 0)))
+    return rA, np.where(L == 63, 64, 128 - rA)
 
 
 def dft(x, axis):  # forward DFT along axis
     return np.fft.fft(x, axis=axis)
 
 
-def model(x0, x1):
+def model(x0, x1, f64=False):
     z = x0 + 1j * x1                       # windowing omitted (linear)
     v = np.empty((64, 16), complex)        # v[lane, reg]
     for a in range(16):
@@ -45,25 +97,22 @@ def model(x0, x1):
     for h in range(2):                     # pass 2: DFT8 over b1 -> c0, twiddle w64^{b0 c0}
         v[:, 8 * h:8 * h + 8] = dft(v[:, 8 * h:8 * h + 8], 1)
         v[:, 8 * h:8 * h + 8] *= np.exp(-2j * np.pi * np.outer(b0, np.arange(8)) / 64)
-    # T2 through a flat LDS image (float2 units, stride 17 per lane row)
-    lds = np.full(64 * 17, np.nan, complex)
-    irr = [[63 * 17, 60 * 17, 61 * 17, 62 * 17, 63 * 17 + 8, 62 * 17 + 8, 61 * 17 + 8, 60 * 17 + 8],
-           [56 * 17, 57 * 17, 58 * 17, 59 * 17, 59 * 17 + 8, 58 * 17 + 8, 57 * 17 + 8, 56 * 17 + 8]]
-    kl = L >> 3
-    for lane in range(64):
+    # T2 through a flat LDS image (complex units): 16 stores, the same for every lane
+    RS = row_stride(f64)
+    lds = np.full(8 * RS, np.nan, complex)
+    base = store_bases(f64)
+    for h in range(2):
         for c in range(8):
-            if kl[lane] != 0:
-                lds[(kl[lane] - 1) * 8 * 17 + b0[lane] + 17 * c] = v[lane, c]
-                lds[(7 - kl[lane]) * 8 * 17 + 8 + b0[lane] + 17 * (7 - c)] = v[lane, 8 + c]
-            else:
-                lds[b0[lane] + irr[0][c]] = v[lane, c]
-                lds[b0[lane] + irr[1][c]] = v[lane, 8 + c]
-    assert not np.isnan(lds.reshape(64, 17)[:, :16]).any()
-    v = np.stack([lds[lane * 17:lane * 17 + 16] for lane in range(64)])
+            addr = base[:, store_reg(h, c)] + store_imm(h, c)
+            assert np.isnan(lds[addr]).all() and len(set(addr)) == 64
+            lds[addr] = v[:, 8 * h + c]
+    assert np.isnan(lds).sum() == 8 * (RS - 128)
+    cl = np.array([col(lane) for lane in range(64)])
+    v = np.stack([np.concatenate([lds[cl[lane] + RS * np.arange(8)], lds[cl[lane] + 64 + RS * np.arange(8)]])
+                  for lane in range(64)])
     v[:, :8] = dft(v[:, :8], 1)           # pass 3
     v[:, 8:] = dft(v[:, 8:], 1)
-    rA = np.where(L < 56, (L >> 3) + 1 + 16 * (L & 7), np.where(L < 60, 8 + 16 * (L - 56), np.where(L < 63, 16 * (L - 59), 0)))
-    rB = np.where(L == 63, 64, 128 - rA)
+    rA, rB = residues()
     P0 = np.full(513, np.nan); P1 = np.full(513, np.nan)
 
     def pw(a, b, k):
@@ -84,11 +133,17 @@ def model(x0, x1):
     return P0, P1
 
 
-rng = np.random.default_rng(0)
-x0, x1 = rng.standard_normal(1024), rng.standard_normal(1024)
-P0, P1 = model(x0, x1)
-R0, R1 = abs(np.fft.rfft(x0)) ** 2, abs(np.fft.rfft(x1)) ** 2
-print("max rel err frame t  :", np.max(abs(P0 - R0) / R0.max()))
-print("max rel err frame t+1:", np.max(abs(P1 - R1) / R1.max()))
-assert np.allclose(P0, R0, rtol=1e-9, atol=1e-9 * R0.max()) and np.allclose(P1, R1, rtol=1e-9, atol=1e-9 * R1.max())
-print("pair model OK")
+def main():
+    rng = np.random.default_rng(0)
+    x0, x1 = rng.standard_normal(1024), rng.standard_normal(1024)
+    for f64 in (False, True):
+        P0, P1 = model(x0, x1, f64)
+        R0, R1 = abs(np.fft.rfft(x0)) ** 2, abs(np.fft.rfft(x1)) ** 2
+        print("max rel err frame t  :", np.max(abs(P0 - R0) / R0.max()))
+        print("max rel err frame t+1:", np.max(abs(P1 - R1) / R1.max()))
+        assert np.allclose(P0, R0, rtol=1e-9, atol=1e-9 * R0.max()) and np.allclose(P1, R1, rtol=1e-9, atol=1e-9 * R1.max())
+    print("pair model OK")
+
+
+if __name__ == "__main__":
+    main()
