@@ -21,6 +21,9 @@
  *   sonar_chroma_stft          <- MusicFeatureExtractor.extractChromaFeatures
  *                                 (fingerprint/extractors/music.go:327) ->
  *                                 ChromaSTFT.ComputeChroma (algorithms/chroma/chroma_stft.go:45)
+ *   sonar_chroma_cqt           <- ChromaCQT.ComputeChroma (algorithms/chroma/chroma_cqt.go:69)
+ *   sonar_chroma_cqt_plan      <- computeCQTKernel's bin count, kernel lengths and FFT size
+ *                                 (chroma_cqt.go:95-165) and computeCQTSpectrogram's frame count (:169-172)
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
  *   sonar_xcorr_params         <- CrossCorrelation.Compute for every type, method and constructor
@@ -287,6 +290,55 @@ int sonar_pitch_yin(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample
 int sonar_chroma_stft(sonar_ctx* ctx, const double* pcm, int64_t n, int64_t n_frames, int32_t hop,
                       int32_t sample_rate, int32_t preprocess, double* chroma /* n_frames x 12 */,
                       int32_t device_ptrs);
+
+/* ---- constant-Q chroma: ChromaCQT.ComputeChroma (algorithms/chroma/chroma_cqt.go:69-92) of
+ * NewChromaCQT(sample_rate, min_freq, max_freq, bins_per_octave, q_factor, tuning_freq) (:43-54;
+ * NewChromaCQTDefault :57-66 is 65.4, 2093.0, 12, 25.0, 440.0), float64 PCM.
+ *   total_bins = int(math.Log2(max_freq / min_freq) * bins_per_octave) (:97-98),
+ *   freq_k = min_freq * math.Pow(2, k / bins_per_octave) (:103),
+ *   kernel_len(f) = int(q_factor * sample_rate / f), made odd, raised to 3, then capped at
+ *   sample_rate / 2 (the capped value may be even); the centre is kernel_len / 2 (:147-165, :123),
+ *   fft_size = nextPowerOfTwo(2 * kernel_len(freq_0)) (:107-108, :315-325),
+ *   n_frames = (n - hop) / hop truncating, 1 when that is <= 0 (:169-172; a negative hop gives one
+ *   frame at sample 0); frame f starts at f * hop and spans fft_size samples, zero-padded past the
+ *   end of the signal (:183-188).
+ * The reference passes each Gaussian-windowed complex exponential through complexToReal, which takes
+ * cmplx.Abs of every tap (:139, :306-312), so kernel k is the FFT of the real sequence
+ * g_k[t] = hypot(w cos(phi), w sin(phi)), w = exp(-(t - centre)^2 / (2 sigma^2)),
+ * sigma = sample_rate / (2 pi freq_k / q_factor), phi = 2 pi freq_k (t - centre) / sample_rate
+ * (:120-135), and the sum of frameFFT[n] * conj(K_k[n]) over all fft_size bins (:198-200) is, by
+ * Parseval, fft_size * sum_{t < kernel_len_k} frame[t] g_k[t].  So
+ *   cqt[f][k] = |fft_size * sum_t pcm[f hop + t] g_k[t]|                                   (:203)
+ * computed as that dot product in float64 (the reference's FFT-domain sum differs from it by its
+ * rounding: 1e-15 of fft_size |frame[:L_k]| |g_k|), and the fold (:213-242, :255-268):
+ *   chroma_bin_k = int(math.Round(69 + 12 log2(freq_k / tuning_freq))) % 12, + 12 if negative,
+ *   chroma[f][c] = sum of cqt[f][k]^2 over the bins of class c, in bin order; each frame is divided
+ *   by its sum only when the sum is > 1e-10; classes no bin maps to stay 0.
+ * The tap table is built on the host and cached in the context per parameter set until sonar_trim.
+ * Results and errors in Go's words: n == 0 -> SONAR_OK with zero frames (Go returns nil, nil) before
+ * anything else is looked at; total_bins == 0 -> SONAR_ERR_PANIC "runtime error: index out of range
+ * [0] with length 0" (:107); total_bins < 0 -> SONAR_ERR_PANIC "runtime error: makeslice: len out
+ * of range" (:101); hop == 0 -> SONAR_ERR_PANIC "runtime error: integer divide by zero" (:169).
+ * Not reproduced (SONAR_ERR_UNSUPPORTED, the message says so): a non-finite or non-positive
+ * min_freq, max_freq, q_factor or tuning_freq; bins_per_octave < 1; sample_rate < 6; a bin count or
+ * tap table beyond the library's limits; non-finite PCM (the reference spreads a NaN through its
+ * FFT's butterflies over the whole fft_size-sample frame span). */
+/* The integer side, host only (no context, no GPU).  kernel_len and chroma_bin are optional arrays of
+ * total_bins entries (call once with both NULL for the count); sum_taps = sum of kernel_len.  n == 0
+ * gives n_frames = 0 whatever hop is.  Returns SONAR_OK, SONAR_ERR_PANIC or SONAR_ERR_UNSUPPORTED as
+ * above (the outputs computed before the error are set: total_bins for the two bin-count panics). */
+int sonar_chroma_cqt_plan(int32_t sample_rate, double min_freq, double max_freq, int32_t bins_per_octave,
+                          double q_factor, double tuning_freq, int64_t n, int64_t hop,
+                          int64_t* total_bins, int64_t* fft_size, int64_t* n_frames, int64_t* sum_taps,
+                          int32_t* kernel_len /* [total_bins] or NULL */,
+                          int32_t* chroma_bin /* [total_bins] or NULL */);
+/* ComputeChroma.  Host pointers: synchronous.  Device pointers (device_ptrs): pcm, chroma and cqt are
+ * device addresses, a null cqt goes to library scratch; the call returns after its kernels have run
+ * (the non-finite scan's answer is read first). */
+int sonar_chroma_cqt(sonar_ctx* ctx, const double* pcm, int64_t n, int64_t hop, int32_t sample_rate,
+                     double min_freq, double max_freq, int32_t bins_per_octave, double q_factor,
+                     double tuning_freq, double* chroma /* n_frames x 12 */,
+                     double* cqt /* n_frames x total_bins, may be NULL */, int32_t device_ptrs);
 
 /* ---- path B: normalized cross-correlation (float64) --------------------
  * corr has 2L+1 entries, L = max(0, min(max_lag, na-1, nb-1)); metrics[10] =

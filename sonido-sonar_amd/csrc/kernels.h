@@ -230,6 +230,28 @@ constexpr int64_t XCORR_FFT_MAX_N = int64_t(1) << 22;
 constexpr int XCORR_FFT_TILE = 4096;   // points whose low levels run in LDS (64 KB)
 int launch_xcorr_fft(const double* xa, int64_t na, const double* xb, int64_t nb, int64_t N, const double2* tw,
                      double2* A, double2* B, double2* C, int64_t L, double* corr, hipStream_t s);
+// ChromaCQT.ComputeChroma (cqt_kernels.hip; chroma_cqt.go:168-268).  The bins are taken in groups of
+// CQT_BK consecutive ones (kernel lengths fall with the bin index, so a group's are alike); group g's
+// taps lie at tab + goff[g] as CQT_BK rows of lpad[g] doubles, lpad[g] = its longest kernel rounded up
+// to 64, each row zero beyond its own kernel length and the rows of bins past the last all zero.
+//   cqt[f][k] = |N * sum_t x[f hop + t] g_k[t]|, x zero past n, f < F, k < K
+//   chroma[f][cls[k]] += cqt[f][k]^2 in bin order, divided by the frame's sum when that is > 1e-10
+// ngroups = ceil(K / CQT_BK); F >= 1; hop is any value when F == 1 (frame 0 starts at sample 0).
+constexpr int CQT_BK = 8;    // bins per group (and per lane's accumulator block)
+constexpr int CQT_FT = 8;    // frames per wave
+struct CqtArgs {
+  const double* x;
+  int64_t n, hop, F;
+  int K, ngroups;
+  double N;               // fft_size
+  const double* tab;
+  const int64_t* goff;    // [ngroups]
+  const int32_t* lpad;    // [ngroups]
+  const int32_t* cls;     // [K] chroma class of each bin
+  double* cqt;            // F x K
+  double* chroma;         // F x 12
+};
+int launch_chroma_cqt(const CqtArgs& a, hipStream_t s);
 // AlignmentAnalyzer.addNoise and flatten2DFeatures (align_kernels.hip)
 int launch_perturb(const double* q, int64_t nq, int dim, double level, double* out, hipStream_t s);
 int launch_first_column(const double* x, int64_t n, int dim, double* out, hipStream_t s);

@@ -7,6 +7,7 @@ API:  ``Context.fingerprint`` ~ ComputeSTFTWithWindow + MFCC.ComputeFrames,
 ``Context.ncc`` ~ CrossCorrelation.Compute, ``Context.xcorr_params`` / ``xcorr`` / ``autocorr`` ~ the
 same for every type, method and constructor, ``Context.dtw`` ~ DTWAlignment.Align,
 ``Context.dtw_params`` ~ NewDTWAlignmentWithParams(...).Align, ``dtw_quality`` ~ GetAlignmentQuality,
+``Context.chroma_cqt`` ~ NewChromaCQT(...).ComputeChroma (``chroma_cqt_plan``: its sizes, host only),
 ``Context.generate_fingerprint`` ~ FingerprintGenerator.GenerateFingerprint,
 ``Context.align_features`` ~ AlignmentExtractor.ExtractAlignmentFeatures.
 
@@ -37,6 +38,7 @@ from ._abi import (  # noqa: F401
     energy_frames,
     pitch_frames,
     fp_kernel_plan,
+    chroma_cqt_plan,
     PLAN_NONE,
     PLAN_PAIR,
     PLAN_WAVE,

@@ -221,6 +221,10 @@ def lib():
                                           C.POINTER(FpConfig), C.POINTER(FpOut)]
     L.sonar_pitch_yin.argtypes = [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int32]
     L.sonar_chroma_stft.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32]
+    L.sonar_chroma_cqt_plan.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int64,
+                                        C.c_int64, _i64p, _i64p, _i64p, _i64p, _vp, _vp]
+    L.sonar_chroma_cqt.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                   C.c_double, C.c_double, _vp, _vp, C.c_int32]
     L.sonar_ncc.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, _vp, C.c_int32]
@@ -383,6 +387,32 @@ def energy_frames(n, W, H):
 
 def pitch_frames(n):
     return int(lib().sonar_pitch_frames(n))
+
+
+_CQT_PLAN_ERRORS = {ERR_PANIC: "the Go reference panics on these parameters (no bins, a negative bin count, or "
+                               "hop 0 with samples to frame); sonar_chroma_cqt reports its runtime error text",
+                    ERR_UNSUPPORTED: "chroma CQT: parameters the library does not reproduce (include/sonar_gpu.h)"}
+
+
+def chroma_cqt_plan(sample_rate, min_freq=65.4, max_freq=2093.0, bins_per_octave=12, q_factor=25.0, tuning_freq=440.0,
+                    n=0, hop=512):
+    """sonar_chroma_cqt_plan (host only): the integer side of NewChromaCQT(...)'s kernel and the frame
+    count of ComputeChroma on n samples at hop -> dict of total_bins, fft_size, n_frames, sum_taps,
+    kernel_len and chroma_bin (int32 arrays of total_bins entries).  n = 0 gives n_frames = 0."""
+    L = lib()
+    v = [C.c_int64() for _ in range(4)]
+    args = (int(sample_rate), float(min_freq), float(max_freq), int(bins_per_octave), float(q_factor),
+            float(tuning_freq), int(n), int(hop))
+    rc = L.sonar_chroma_cqt_plan(*args, *[C.byref(x) for x in v], None, None)
+    if rc != OK:
+        raise SonarError(rc, _CQT_PLAN_ERRORS.get(rc, "sonar_chroma_cqt_plan"))
+    K = v[0].value
+    klen, cls = np.zeros(K, np.int32), np.zeros(K, np.int32)
+    rc = L.sonar_chroma_cqt_plan(*args, *[C.byref(x) for x in v], _ptr(klen), _ptr(cls))
+    if rc != OK:
+        raise SonarError(rc, _CQT_PLAN_ERRORS.get(rc, "sonar_chroma_cqt_plan"))
+    return {"total_bins": K, "fft_size": v[1].value, "n_frames": v[2].value, "sum_taps": v[3].value,
+            "kernel_len": klen, "chroma_bin": cls}
 
 
 def multi_shard(n, W, H, n_shards, shard):
@@ -650,6 +680,36 @@ class Context:
         self._check(self._L.sonar_chroma_stft(self._h, _ptr(pcm), len(pcm), n_frames, hop, sample_rate,
                                               int(preprocess), _ptr(out), 0))
         return out
+
+    def chroma_cqt(self, pcm, hop, sample_rate, min_freq=65.4, max_freq=2093.0, bins_per_octave=12, q_factor=25.0,
+                   tuning_freq=440.0, return_cqt=False):
+        """NewChromaCQT(sample_rate, min_freq, max_freq, bins_per_octave, q_factor, tuning_freq)
+        .ComputeChroma(pcm, hop) (sonar_chroma_cqt; the defaults are NewChromaCQTDefault's) -> the
+        (n_frames, 12) chroma, with return_cqt also the (n_frames, total_bins) CQT magnitudes.  An empty
+        signal gives a (0, 12) array (Go returns nil, nil)."""
+        pcm = _f64(pcm)
+        n = len(pcm)
+        params = (int(sample_rate), float(min_freq), float(max_freq), int(bins_per_octave), float(q_factor),
+                  float(tuning_freq))
+        if n == 0:
+            return (np.zeros((0, 12)), np.zeros((0, 0))) if return_cqt else np.zeros((0, 12))
+        v = [C.c_int64() for _ in range(4)]
+        F = K = 0
+        if self._L.sonar_chroma_cqt_plan(*params, n, int(hop), *[C.byref(x) for x in v], None, None) == OK:
+            K, F = v[0].value, v[2].value                  # otherwise the call below reports the error
+        chroma = np.zeros((F, 12))
+        cqt = np.zeros((F, K)) if return_cqt else None
+        self._check(self._L.sonar_chroma_cqt(self._h, _ptr(pcm), n, int(hop), *params, _ptr(chroma), _ptr(cqt), 0))
+        return (chroma, cqt) if return_cqt else chroma
+
+    def chroma_cqt_device(self, pcm_ptr, n, hop, sample_rate, chroma_ptr, min_freq=65.4, max_freq=2093.0,
+                          bins_per_octave=12, q_factor=25.0, tuning_freq=440.0, cqt_ptr=None):
+        """chroma_cqt on device memory (device_ptrs = 1): pcm (n doubles), chroma (n_frames x 12) and the
+        optional CQT array (n_frames x total_bins; None: library scratch) are device addresses; the
+        sizes are chroma_cqt_plan's."""
+        self._check(self._L.sonar_chroma_cqt(self._h, pcm_ptr, int(n), int(hop), int(sample_rate), float(min_freq),
+                                             float(max_freq), int(bins_per_octave), float(q_factor),
+                                             float(tuning_freq), chroma_ptr, cqt_ptr, 1))
 
     def music_alignment_features(self, pcm, sample_rate, stft_window=1024, stft_hop=256, feature_window=1024,
                                  feature_hop=256):
