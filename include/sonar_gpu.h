@@ -24,6 +24,11 @@
  *   sonar_chroma_cqt           <- ChromaCQT.ComputeChroma (algorithms/chroma/chroma_cqt.go:69)
  *   sonar_chroma_cqt_plan      <- computeCQTKernel's bin count, kernel lengths and FFT size
  *                                 (chroma_cqt.go:95-165) and computeCQTSpectrogram's frame count (:169-172)
+ *   sonar_chroma_similarity    <- ChromaSequenceSimilarity.ComputeSimilarity, all six methods
+ *                                 (algorithms/chroma/chroma_similarity.go:86-538)
+ *   sonar_chroma_frame_matrix  <- ChromaVectorAnalyzer.Distance / Similarity / CircularShift for every
+ *                                 frame pair (chroma_vector.go:145-216; stats/distance.go)
+ *   sonar_chroma_similarity_plan <- its integer side: sample step, OTI ranges, the DTW band rule
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
  *   sonar_xcorr_params         <- CrossCorrelation.Compute for every type, method and constructor
@@ -339,6 +344,86 @@ int sonar_chroma_cqt(sonar_ctx* ctx, const double* pcm, int64_t n, int64_t hop, 
                      double min_freq, double max_freq, int32_t bins_per_octave, double q_factor,
                      double tuning_freq, double* chroma /* n_frames x 12 */,
                      double* cqt /* n_frames x total_bins, may be NULL */, int32_t device_ptrs);
+
+/* ---- chroma sequence similarity (float64) --------------------------------
+ * ChromaSequenceSimilarity.ComputeSimilarity (algorithms/chroma/chroma_similarity.go:86-538) over
+ * ChromaVectorAnalyzer.Distance / Similarity / CircularShift (chroma_vector.go:145-216) and the frame
+ * metrics of stats/distance.go (:28-108, :247-294, :341-369).  q and r are nq x dim and nr x dim
+ * row-major chroma frames, dim >= 1 (12, 24 and 36 are the reference's sizes).  Every array pointer
+ * of a call is of one kind, host or device; the library tells which from q (r when nq == 0).
+ * Frame metric: Distance is the metric's DistanceFunc, any value outside 0..6 is Euclidean.
+ * Similarity is 1 - d/2 for Cosine and Pearson and exp(-d) for every other value.  Pearson is
+ * 1 - |corr|; Cosine is 1 when a norm is 0; KL, JS and Hellinger normalise each frame to a
+ * probability vector first (positive values only, an all-non-positive frame becomes uniform), and
+ * JS normalises its normalised arguments a second time inside KLDivergenceFunc (:276, :250).
+ * CircularShift: value k of the shifted query frame is q[(k + shift) % dim].
+ * Never read by the reference, so not carried here: FrameStackSize, FrameStackStride,
+ * NormalizeSimilarity, ComputationTime. */
+#define SONAR_CHROMA_SIM_DIRECT 0
+#define SONAR_CHROMA_SIM_BINARY 1
+#define SONAR_CHROMA_SIM_SMITH_WATERMAN 2
+#define SONAR_CHROMA_SIM_DTW 3
+#define SONAR_CHROMA_SIM_QMAX 4
+#define SONAR_CHROMA_SIM_OTI 5
+#define SONAR_CHROMA_DIST_EUCLIDEAN 0
+#define SONAR_CHROMA_DIST_MANHATTAN 1
+#define SONAR_CHROMA_DIST_COSINE 2
+#define SONAR_CHROMA_DIST_PEARSON 3
+#define SONAR_CHROMA_DIST_KL 4
+#define SONAR_CHROMA_DIST_JS 5
+#define SONAR_CHROMA_DIST_HELLINGER 6
+/* ChromaVectorAnalyzer.Distance (as_similarity = 0) or Similarity of CircularShift(q_i, shift) and
+ * r_j for every pair: out[i * nr + j].  shift < 0 is Go's index panic (SONAR_ERR_PANIC). */
+int sonar_chroma_frame_matrix(sonar_ctx* ctx, const double* q, int64_t nq, const double* r, int64_t nr,
+                              int32_t dim, int32_t metric, int32_t shift, int32_t as_similarity, double* out);
+/* ComputeSimilarity.  method outside 0..5 runs Direct, as the reference's default case does.
+ *   Direct  matrix = Similarity(q_i, r_j); overall = the sum over the matrix / (nq nr) (the reference
+ *           adds serially in row-major order, this adds as a tree: they differ by at most
+ *           nq nr 2^-53 mean|sim|).  With transposition_invariant the query is shifted by
+ *           findBestTransposition's shift (:450-479: step = int(max(1, nq / 50)) for rows and columns,
+ *           12 sampled means added in Go's order, the first strictly greater than the running best
+ *           from 0.0 wins, NaN never) and overall = that best mean.
+ *   Binary  Direct's matrix > binary_threshold as 1.0 / 0.0; overall = matches / (nq nr).
+ *   QMax    Direct's matrix; overall = max(0, largest non-NaN entry) (every cell lies on one diagonal).
+ *   OTI     per shift 0..11 the similarities of j in [max(0, i - R), min(nr, i + R + 1)), R =
+ *           oti_radius, the rest 0, added in Go's order; avg = total / (nq nr), the full grid; the
+ *           first avg strictly greater than the running best from 0.0 wins.  If none does the matrix
+ *           is nil (*matrix_is_nil = 1, matrix untouched), overall 0, transposition 0.  Ignores
+ *           transposition_invariant.
+ *   Smith-Waterman  S = max(0, max(S[i-1][j-1] + sim, max(S[i-1][j] - 0.1, S[i][j-1] - 0.1))) with
+ *           math.Max; matrix = S[1:][1:], the scores; the path walks back from the first row-major
+ *           maximum > 0 while S > 0, by the codes of `switch maxVal {case match, delete, insert}`
+ *           (float equality, 0 when none is equal); points (i - 1, j - 1, S[i][j]); overall =
+ *           maxScore / len(path), 0 / 0 = NaN when nothing scores.  No transposition.
+ *   DTW     cost = Distance; acc[0][0] = cost[0][0], first row and column cumulative, interior
+ *           cost + math.Min(up, math.Min(left, diag)); with dtw_band_radius R > 0 a column j >= 1 with
+ *           |j - int(float64(j nq) / float64(nr))| > R is skipped in every row i >= 1 and stays 0
+ *           (never with nq == nr); the path walks back from the end with <=, diagonal, up, left, and
+ *           does not hold (0, 0); points (i, j, acc[i][j]); overall = exp(-acc[nq-1][nr-1] /
+ *           len(path)) (1 x 1: a division by 0); matrix = exp(-cost).
+ * matrix (nq x nr) may be NULL: Direct, Binary, QMax and OTI then reduce without storing it and
+ * take any size; Smith-Waterman and DTW keep their DP matrix in device scratch and take nq nr <= 2^30
+ * cells (SONAR_ERR_UNSUPPORTED beyond).  path_q, path_r, path_score (nq + nr entries each, any may be
+ * NULL) and *path_len are written by Smith-Waterman and DTW only.
+ * Empty input in Go's words: DTW -> SONAR_ERR_PANIC "runtime error: index out of range [0] with length
+ * 0"; the others return SONAR_OK and launch nothing: overall NaN (Direct, Binary, Smith-Waterman),
+ * 0 (QMax, Direct with transposition_invariant), OTI nil. */
+int sonar_chroma_similarity(sonar_ctx* ctx, const double* q, int64_t nq, const double* r, int64_t nr,
+                            int32_t dim, int32_t method, int32_t metric, double binary_threshold,
+                            int32_t oti_radius, int32_t dtw_band_radius, int32_t transposition_invariant,
+                            double* matrix /* nq*nr, nullable */, int32_t* matrix_is_nil, double* overall,
+                            int32_t* best_transposition, int32_t* path_q, int32_t* path_r,
+                            double* path_score /* nq+nr each, nullable */, int64_t* path_len);
+/* The integer side, host only (no context, no GPU): findBestTransposition's step and its pairs per
+ * shift, OTI's computed cells per shift, the columns j >= 1 the DTW band rule skips (0 when
+ * dtw_band_radius <= 0 or nq < 2), and the device scratch of a host-pointer call with a matrix. */
+int sonar_chroma_similarity_plan(int32_t method, int64_t nq, int64_t nr, int32_t dim, int32_t oti_radius,
+                                 int32_t dtw_band_radius, int64_t* sample_step, int64_t* sampled_pairs,
+                                 int64_t* oti_cells, int64_t* dtw_skipped_columns, int64_t* scratch_bytes);
+/* HIP-event times (ms) of the last chroma similarity or frame matrix call on this context: ms4[0] the
+ * frame matrix (with the row preparation), ms4[1] the ordered sums, ms4[2] the Smith-Waterman / DTW
+ * fill, ms4[3] the traceback; 0 for a family the call did not run -- diagnostics. */
+int sonar_chroma_similarity_last_timing(sonar_ctx* ctx, double* ms4);
 
 /* ---- path B: normalized cross-correlation (float64) --------------------
  * corr has 2L+1 entries, L = max(0, min(max_lag, na-1, nb-1)); metrics[10] =

@@ -79,6 +79,10 @@ struct sonar_ctx {
   // sonar_fingerprint_batch: its segment table's pinned staging is rewritten only after the previous
   // call's upload of it has completed (this event)
   hipEvent_t fpb_ev = nullptr;
+  // sonar_chroma_similarity's kernel families (chroma_sim_api.cpp): an event pair each for the frame
+  // matrix, the ordered sums, the DP fill and the traceback, and the last call's times
+  hipEvent_t csim_ev[8] = {};
+  double csim_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 // Named float64 arrays + scalars.  An array either owns its values (v) or points into a block the

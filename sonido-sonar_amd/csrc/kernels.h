@@ -472,4 +472,58 @@ int sort_match_keys(const double* keys, double* keys2, const int64_t* vals, int6
 int launch_match_gather(const sonar_similarity* sims, const int64_t* vals_sorted, const int64_t* counts,
                         int64_t nq, int64_t nc, int K, sonar_match* out, hipStream_t s);
 
+// ChromaSequenceSimilarity (chroma_sim_kernels.hip; chroma_similarity.go, chroma_vector.go:145-216,
+// stats/distance.go).  The metric values are SONAR_CHROMA_DIST_*; any other value is Euclidean.
+enum ChromaMetric : int { CHROMA_EUCLIDEAN = 0, CHROMA_MANHATTAN = 1, CHROMA_COSINE = 2, CHROMA_PEARSON = 3,
+                          CHROMA_KL = 4, CHROMA_JS = 5, CHROMA_HELLINGER = 6 };
+constexpr int CHROMA_DP_T = 64;   // tile edge of the Smith-Waterman / DTW wavefront
+// prepared rows: 2 dim + 2 doubles each (see chroma_prepare_kernel)
+inline int chroma_row_len(int dim) { return 2 * dim + 2; }
+// out[(sh * n + row) * row_len] = row `row` of x under CircularShift(shift0 + sh), sh < nshift
+int launch_chroma_prepare(const double* x, int64_t n, int dim, int metric, int shift0, int nshift, double* out,
+                          hipStream_t s);
+struct ChromaMatArgs {
+  const double *qp, *rp;         // prepared rows
+  int64_t nq, nr;
+  int dim, metric;
+  int mode;                      // 0 Distance, 1 Similarity
+  int binary;                    // value > thr -> 1.0 / 0.0, hits added to *count
+  double thr;
+  int banded;                    // OTI: cells outside max(0, i - radius) <= j < i + radius + 1 are 0
+  int64_t radius;
+  double* out;                   // nq x nr, or null (fused reductions only)
+  double* partial;               // [chroma_matrix_blocks] per-block sums, or null
+  unsigned long long* count;     // or null
+  unsigned long long* maxbits;   // bits of max(0, max of the non-NaN values), or null; caller zeroes
+};
+int64_t chroma_matrix_blocks(int64_t nq, int64_t nr);
+int launch_chroma_matrix(const ChromaMatArgs& a, hipStream_t s);   // -1: more rows than one launch takes
+int launch_chroma_sum_partials(const double* p, int64_t n, double* out, hipStream_t s);
+struct ChromaOrdArgs {
+  const double* qp;              // 12 x nq prepared query rows, shift-major
+  const double* rp;
+  int64_t nq, nr;
+  int dim, metric;
+  int64_t step;                  // findBestTransposition's sample step (rows and columns); 1 when banded
+  int banded;                    // the OTI column range of every row
+  int64_t radius;
+  double* totals;                // [12]
+};
+int launch_chroma_ordered(const ChromaOrdArgs& a, hipStream_t s);
+int launch_chroma_exp_neg(const double* in, int64_t n, double* out, hipStream_t s);
+struct ChromaDpArgs {
+  double* M;                     // nq x nr: frame similarities (SW) / distances (DTW) in, scores / acc out
+  int64_t nq, nr, ntj;           // ntj = ceil(nr / CHROMA_DP_T)
+  int dtw;
+  const uint8_t* skip;           // DTW: [nr] columns the band rule skips, or null
+  uint8_t* tb;                   // SW: nq x nr traceback codes
+  double* tile_best;             // SW: per tile, its best score and that score's first row-major index
+  int64_t* tile_idx;
+};
+int launch_chroma_dp(const ChromaDpArgs& a, hipStream_t s);
+int launch_chroma_sw_best(const double* tile_best, const int64_t* tile_idx, int64_t ntiles, double* best, int64_t* idx,
+                          hipStream_t s);
+int launch_chroma_traceback(const double* M, const uint8_t* tb, int64_t nq, int64_t nr, int dtw, const int64_t* start,
+                            int32_t* pq, int32_t* pr, double* ps, int64_t cap, int64_t* plen, hipStream_t s);
+
 }  // namespace sonar

@@ -394,6 +394,8 @@ void sonar_destroy(sonar_ctx* c) {
   if (c->ev1) hipEventDestroy(c->ev1);
   for (auto& e : c->dtw_ev)
     if (e) hipEventDestroy(e);
+  for (auto& e : c->csim_ev)
+    if (e) hipEventDestroy(e);
   for (auto& e : c->side_ev)
     if (e) hipEventDestroy(e);
   if (c->side) hipStreamDestroy(c->side);

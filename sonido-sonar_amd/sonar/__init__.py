@@ -8,6 +8,8 @@ API:  ``Context.fingerprint`` ~ ComputeSTFTWithWindow + MFCC.ComputeFrames,
 same for every type, method and constructor, ``Context.dtw`` ~ DTWAlignment.Align,
 ``Context.dtw_params`` ~ NewDTWAlignmentWithParams(...).Align, ``dtw_quality`` ~ GetAlignmentQuality,
 ``Context.chroma_cqt`` ~ NewChromaCQT(...).ComputeChroma (``chroma_cqt_plan``: its sizes, host only),
+``Context.chroma_similarity`` ~ ChromaSequenceSimilarity.ComputeSimilarity (``chroma_frame_matrix``: its
+frame distances / similarities, ``chroma_similarity_plan``: its integer side, host only),
 ``Context.generate_fingerprint`` ~ FingerprintGenerator.GenerateFingerprint,
 ``Context.align_features`` ~ AlignmentExtractor.ExtractAlignmentFeatures.
 
@@ -39,6 +41,9 @@ from ._abi import (  # noqa: F401
     pitch_frames,
     fp_kernel_plan,
     chroma_cqt_plan,
+    chroma_similarity_plan,
+    CHROMA_SIM_METHODS,
+    CHROMA_DIST_METRICS,
     PLAN_NONE,
     PLAN_PAIR,
     PLAN_WAVE,

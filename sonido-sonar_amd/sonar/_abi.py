@@ -31,6 +31,9 @@ DTW_QUALITY_KEYS = ["path_efficiency", "diagonal_ratio", "average_cost", "normal
 # CorrelationType / CorrelationMethod (SONAR_CORR_*), correlation.go:12-41
 CORR_TYPES = {"pearson": 0, "spearman": 1, "kendall": 2, "ncc": 3, "zncc": 4}
 CORR_METHODS = {"time": 0, "frequency": 1, "sliding": 2}
+# ChromaSimilarityMethod / the frame metrics (SONAR_CHROMA_SIM_* / SONAR_CHROMA_DIST_*)
+CHROMA_SIM_METHODS = {"direct": 0, "binary": 1, "smith_waterman": 2, "dtw": 3, "qmax": 4, "oti": 5}
+CHROMA_DIST_METRICS = {"euclidean": 0, "manhattan": 1, "cosine": 2, "pearson": 3, "kl": 4, "js": 5, "hellinger": 6}
 NCC_KEYS = ["peak_correlation", "peak_lag", "peak_index", "p_value", "snr", "sharpness",
             "second_peak", "peak_to_sidelobe", "overlap_length", "num_lags"]
 
@@ -225,6 +228,14 @@ def lib():
                                         C.c_int64, _i64p, _i64p, _i64p, _i64p, _vp, _vp]
     L.sonar_chroma_cqt.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                    C.c_double, C.c_double, _vp, _vp, C.c_int32]
+    L.sonar_chroma_frame_matrix.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, _vp]
+    L.sonar_chroma_similarity.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_int32, C.c_int32, C.c_int32, _vp, C.POINTER(C.c_int32), _d,
+                                          C.POINTER(C.c_int32), _vp, _vp, _vp, _i64p]
+    L.sonar_chroma_similarity_plan.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                               _i64p, _i64p, _i64p, _i64p, _i64p]
+    L.sonar_chroma_similarity_last_timing.argtypes = [_vp, C.POINTER(C.c_double)]
     L.sonar_ncc.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, _vp, C.c_int32]
@@ -413,6 +424,23 @@ def chroma_cqt_plan(sample_rate, min_freq=65.4, max_freq=2093.0, bins_per_octave
         raise SonarError(rc, _CQT_PLAN_ERRORS.get(rc, "sonar_chroma_cqt_plan"))
     return {"total_bins": K, "fft_size": v[1].value, "n_frames": v[2].value, "sum_taps": v[3].value,
             "kernel_len": klen, "chroma_bin": cls}
+
+
+def _chroma_enum(table, v):
+    return table[v] if isinstance(v, str) else int(v)
+
+
+def chroma_similarity_plan(method, nq, nr, dim=12, oti_radius=10, dtw_band_radius=50):
+    """sonar_chroma_similarity_plan (host only): the integer side of ComputeSimilarity -> dict of
+    sample_step and sampled_pairs (findBestTransposition, per shift), oti_cells (per shift),
+    dtw_skipped_columns (the columns j >= 1 the band rule leaves 0) and scratch_bytes."""
+    v = [C.c_int64() for _ in range(5)]
+    rc = lib().sonar_chroma_similarity_plan(_chroma_enum(CHROMA_SIM_METHODS, method), int(nq), int(nr), int(dim),
+                                            int(oti_radius), int(dtw_band_radius), *[C.byref(x) for x in v])
+    if rc != OK:
+        raise SonarError(rc, "sonar_chroma_similarity_plan: negative frame count or dim < 1")
+    return dict(zip(("sample_step", "sampled_pairs", "oti_cells", "dtw_skipped_columns", "scratch_bytes"),
+                    [x.value for x in v]))
 
 
 def multi_shard(n, W, H, n_shards, shard):
@@ -701,6 +729,76 @@ class Context:
         cqt = np.zeros((F, K)) if return_cqt else None
         self._check(self._L.sonar_chroma_cqt(self._h, _ptr(pcm), n, int(hop), *params, _ptr(chroma), _ptr(cqt), 0))
         return (chroma, cqt) if return_cqt else chroma
+
+    @staticmethod
+    def _chroma_frames(x):
+        x = _f64(x)
+        return x.reshape(0, 0) if x.size == 0 else (x[:, None] if x.ndim == 1 else x)
+
+    def chroma_frame_matrix(self, q, r, metric="cosine", shift=0, as_similarity=False):
+        """ChromaVectorAnalyzer.Distance (or Similarity) of CircularShift(q[i], shift) and r[j] for every
+        pair (sonar_chroma_frame_matrix) -> the (nq, nr) matrix.  metric: a CHROMA_DIST_METRICS name
+        or value (unknown values are Euclidean, as in Go)."""
+        q, r = self._chroma_frames(q), self._chroma_frames(r)
+        nq, nr = q.shape[0], r.shape[0]
+        dim = q.shape[1] if nq else (r.shape[1] if nr else 1)
+        out = np.zeros((nq, nr))
+        self._check(self._L.sonar_chroma_frame_matrix(self._h, _ptr(q) if nq else None, nq, _ptr(r) if nr else None,
+                                                      nr, dim, _chroma_enum(CHROMA_DIST_METRICS, metric), int(shift),
+                                                      int(bool(as_similarity)), _ptr(out) if out.size else None))
+        return out
+
+    def chroma_frame_matrix_device(self, q_ptr, nq, r_ptr, nr, dim, out_ptr, metric="cosine", shift=0,
+                                   as_similarity=False):
+        """chroma_frame_matrix on device memory: q, r and the nq x nr output are device addresses."""
+        self._check(self._L.sonar_chroma_frame_matrix(self._h, q_ptr, int(nq), r_ptr, int(nr), int(dim),
+                                                      _chroma_enum(CHROMA_DIST_METRICS, metric), int(shift),
+                                                      int(bool(as_similarity)), out_ptr))
+
+    def chroma_similarity(self, q, r, method="direct", metric="cosine", binary_threshold=0.4, oti_radius=10,
+                          dtw_band_radius=50, transposition_invariant=False, matrix=True):
+        """NewChromaSequenceSimilarityWithParams(...).ComputeSimilarity(q, r) (sonar_chroma_similarity;
+        the defaults are NewChromaSequenceSimilarity's) -> dict of matrix ((nq, nr); None when the
+        reference's is nil or with matrix=False, which does not materialise it), overall,
+        best_transposition, path_q, path_r, path_score (empty unless Smith-Waterman or DTW)."""
+        q, r = self._chroma_frames(q), self._chroma_frames(r)
+        nq, nr = q.shape[0], r.shape[0]
+        dim = q.shape[1] if nq else (r.shape[1] if nr else 1)
+        mat = np.zeros((nq, nr)) if matrix else None
+        cap = nq + nr + 1
+        pq, pr, ps = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap)
+        nil, best, overall, plen = C.c_int32(), C.c_int32(), C.c_double(), C.c_int64()
+        self._check(self._L.sonar_chroma_similarity(
+            self._h, _ptr(q) if nq else None, nq, _ptr(r) if nr else None, nr, dim,
+            _chroma_enum(CHROMA_SIM_METHODS, method), _chroma_enum(CHROMA_DIST_METRICS, metric),
+            float(binary_threshold), int(oti_radius), int(dtw_band_radius), int(bool(transposition_invariant)),
+            _ptr(mat) if mat is not None and mat.size else None, C.byref(nil), C.byref(overall), C.byref(best),
+            _ptr(pq), _ptr(pr), _ptr(ps), C.byref(plen)))
+        P = plen.value
+        return {"matrix": None if nil.value or mat is None else mat, "overall": overall.value,
+                "best_transposition": best.value, "path_q": pq[:P], "path_r": pr[:P], "path_score": ps[:P]}
+
+    def chroma_similarity_device(self, q_ptr, nq, r_ptr, nr, dim, method="direct", metric="cosine",
+                                 binary_threshold=0.4, oti_radius=10, dtw_band_radius=50,
+                                 transposition_invariant=False, matrix_ptr=None, path_q_ptr=None, path_r_ptr=None,
+                                 path_score_ptr=None):
+        """chroma_similarity on device memory: q, r, the optional nq x nr matrix and the optional path
+        arrays (nq + nr entries each) are device addresses -> dict of matrix_is_nil, overall,
+        best_transposition, path_len."""
+        nil, best, overall, plen = C.c_int32(), C.c_int32(), C.c_double(), C.c_int64()
+        self._check(self._L.sonar_chroma_similarity(
+            self._h, q_ptr, int(nq), r_ptr, int(nr), int(dim), _chroma_enum(CHROMA_SIM_METHODS, method),
+            _chroma_enum(CHROMA_DIST_METRICS, metric), float(binary_threshold), int(oti_radius), int(dtw_band_radius),
+            int(bool(transposition_invariant)), matrix_ptr, C.byref(nil), C.byref(overall), C.byref(best),
+            path_q_ptr, path_r_ptr, path_score_ptr, C.byref(plen)))
+        return {"matrix_is_nil": bool(nil.value), "overall": overall.value, "best_transposition": best.value,
+                "path_len": plen.value}
+
+    def chroma_similarity_last_timing(self):
+        """(frame matrix, ordered sums, DP fill, traceback) HIP-event ms of the last chroma similarity call."""
+        v = (C.c_double * 4)()
+        self._check(self._L.sonar_chroma_similarity_last_timing(self._h, v))
+        return tuple(v)
 
     def chroma_cqt_device(self, pcm_ptr, n, hop, sample_rate, chroma_ptr, min_freq=65.4, max_freq=2093.0,
                           bins_per_octave=12, q_factor=25.0, tuning_freq=440.0, cqt_ptr=None):
