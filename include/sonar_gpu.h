@@ -29,6 +29,13 @@
  *   sonar_chroma_frame_matrix  <- ChromaVectorAnalyzer.Distance / Similarity / CircularShift for every
  *                                 frame pair (chroma_vector.go:145-216; stats/distance.go)
  *   sonar_chroma_similarity_plan <- its integer side: sample step, OTI ranges, the DTW band rule
+ *   sonar_spectral_peaks       <- SpectralPeaks.DetectPeaks per spectrum row
+ *                                 (algorithms/harmonic/spectral_peaks.go:36-100)
+ *   sonar_hpcp_from_spectrum   <- HPCP.ComputeFromSpectrum per spectrum row (algorithms/chroma/hpcp.go:205-221)
+ *   sonar_hpcp                 <- SpectralAnalyzer.ComputeSTFT magnitudes -> HPCP.ComputeFromSpectrum per frame
+ *   sonar_hpcp_table           <- frequencyToPitchClass, addPeakContribution, computeWindowWeight and
+ *                                 addHarmonicContributions per FFT bin (hpcp.go:224-321)
+ *   sonar_hpcp_plan            <- the frame count and the chunks sonar_hpcp works in
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
  *   sonar_xcorr_params         <- CrossCorrelation.Compute for every type, method and constructor
@@ -424,6 +431,110 @@ int sonar_chroma_similarity_plan(int32_t method, int64_t nq, int64_t nr, int32_t
  * frame matrix (with the row preparation), ms4[1] the ordered sums, ms4[2] the Smith-Waterman / DTW
  * fill, ms4[3] the traceback; 0 for a family the call did not run -- diagnostics. */
 int sonar_chroma_similarity_last_timing(sonar_ctx* ctx, double* ms4);
+
+/* ---- spectral peaks and the harmonic pitch class profile (float64) --------
+ * SpectralPeaks.DetectPeaks (algorithms/harmonic/spectral_peaks.go:36-100) on each of F rows of K
+ * magnitudes, for NewSpectralPeaks(sample_rate, min_height, min_distance_hz, max_peaks) and
+ * DetectPeaks(row, window_size):
+ *   a candidate is a bin 1 <= i <= K - 2 with row[i] > row[i-1], row[i] > row[i+1] and row[i] >=
+ *   min_height (a NaN makes every comparison false; +Inf is a magnitude like any other);
+ *   min_distance_bins = max(int(min_distance_hz / (sample_rate / window_size)), 1).  Strict local
+ *   maxima are 2 bins apart, so the distance rule acts from 3 on.  The reference's loop (:56-73) stops
+ *   at the first kept peak closer than that, replaces it when the candidate is strictly larger and
+ *   drops the candidate otherwise; kept peaks stay pairwise at least min_distance_bins apart, so that
+ *   peak is always the last kept one: a serial greedy, not a cluster maximum.
+ *   The kept peaks are sorted by magnitude, descending (:90-92, sort.Slice: Go leaves the order of
+ *   equal magnitudes open; here equal magnitudes come in ascending bin order) and cut to max_peaks.
+ *   frequency = float64(bin) * (sample_rate / window_size).  Phase (0) and Harmonic (-1) are constants
+ *   and are not returned.
+ * Outputs: count[F]; bin, magnitude and frequency (frequency may be NULL) have F rows of
+ * P = sonar_spectral_peaks_width(K, max_peaks) = min(max_peaks, max((K - 1) / 2, 0)) slots, the slots
+ * past count[f] are 0.  F == 0 or K == 0 -> SONAR_OK, zero counts (Go returns before it looks at
+ * anything else); max_peaks < 0 -> SONAR_ERR_PANIC "runtime error: slice bounds out of range [:-1]"
+ * (:95-97).  Not reproduced (SONAR_ERR_UNSUPPORTED): sample_rate or window_size <= 0; K > 8192. */
+int64_t sonar_spectral_peaks_width(int64_t K, int64_t max_peaks);
+int sonar_spectral_peaks(sonar_ctx* ctx, const double* mag /* F x K */, int64_t F, int32_t K, int32_t window_size,
+                         int32_t sample_rate, double min_height, double min_distance_hz, int32_t max_peaks,
+                         int32_t* count /* F */, int32_t* bin /* F x P */, double* magnitude /* F x P */,
+                         double* frequency /* F x P or NULL */, int32_t device_ptrs);
+
+/* HPCPParams (algorithms/chroma/hpcp.go:11-26).  weight_type: Go's strings "none", "cosine",
+ * "squared_cosine"; any other value is "none", as the reference's default cases are. */
+#define SONAR_HPCP_WEIGHT_NONE 0
+#define SONAR_HPCP_WEIGHT_COSINE 1
+#define SONAR_HPCP_WEIGHT_SQUARED_COSINE 2
+typedef struct sonar_hpcp_params {
+  int32_t size;               /* Size: bins of the profile (12, 24, 36) */
+  int32_t harmonics_removal;  /* HarmonicsRemoval: removes nothing, only switches the harmonic additions off */
+  int32_t normalized;         /* Normalized: common.Normalizer(Energy) */
+  int32_t weight_type;        /* WeightType */
+  int32_t max_shifted;        /* MaxShifted */
+  int32_t non_linear;         /* NonLinear: log(1 + x) on positive bins */
+  int32_t band_preset;        /* BandPreset: peaks below split_freq weigh double */
+  int32_t max_harmonics;      /* MaxHarmonics: harmonics 2..max_harmonics are added */
+  double reference_freq;      /* ReferenceFreq */
+  double window_size;         /* WindowSize, semitones */
+  double min_freq;            /* MinFreq */
+  double max_freq;            /* MaxFreq */
+  double split_freq;          /* SplitFreq */
+  double harmonics_strength;  /* HarmonicsStrength */
+} sonar_hpcp_params;
+/* NewHPCP's values (hpcp.go:54-75): 12, 440, no removal, normalized, cosine, 1.0, not shifted, linear,
+ * band preset, 40, 5000, 500, 1.0, 0 harmonics. */
+void sonar_hpcp_params_default(sonar_hpcp_params* p);
+
+/* HPCP.ComputeFromSpectrum(row, window_size) (hpcp.go:205-221) of NewHPCPWithParams(sample_rate,
+ * params) on each of F rows of K magnitudes: DetectPeaks with the reference's fixed (1e-5, 20.0 Hz,
+ * 60), then ComputeFromSpectralPeaks (:147-202).  K is the row length whatever window_size is (the
+ * chord detector passes all window_size bins; the mirror half is cut by max_freq only).
+ * Per peak, in sorted order: skipped when f < min_freq || f > max_freq; pc = mod(69 + 12
+ * log2(f / reference_freq), 12), + 12 if negative, times size / 12; weight = magnitude, doubled when
+ * band_preset and f < split_freq; addPeakContribution (:254-281) over the unwrapped bins
+ * floor(pc - w/2) .. ceil(pc + w/2), w = window_size size / 12, each within w/2 (distance folded at
+ * size/2) adding weight * window_weight to its wrapped bin; with max_harmonics > 0 and no
+ * harmonics_removal the harmonics h = 2.. of f h, weight magnitude * (harmonics_strength / h), until
+ * the first above max_freq.  Then non_linear, normalized (divided by sqrt(sum x^2) only when sum x^2
+ * >= 1e-10), max_shifted (the identity up to rounding), energy = sqrt(sum x^2),
+ * entropy = -sum p log2 p over the positive bins (0 when the sum is 0).
+ * A peak's frequency is bin * sample_rate / window_size, so everything transcendental is a function
+ * of the bin: the library builds the contribution table of sonar_hpcp_table on the host, caches it in
+ * the context per parameter set until sonar_trim, and the device adds (magnitude * factor) *
+ * window_weight, two roundings each, in the reference's program order.
+ * hpcp is F x size; energy and entropy (F each) may be NULL.
+ * size < 0 -> SONAR_ERR_PANIC "runtime error: makeslice: len out of range"; size == 0 -> SONAR_OK, an
+ * empty profile, energy 0, entropy 0.  Not reproduced (SONAR_ERR_UNSUPPORTED, the message says which):
+ * a non-finite or non-positive reference_freq; a non-finite or negative window_size; sample_rate or
+ * the STFT window_size <= 0; size > 120, max_harmonics > 16, K > 8192, window_size > 12 semitones, a
+ * table of more than 2^24 entries.  Non-finite magnitudes are no error: they follow IEEE comparisons
+ * as in Go. */
+int sonar_hpcp_from_spectrum(sonar_ctx* ctx, const double* mag /* F x K */, int64_t F, int32_t K,
+                             int32_t window_size, int32_t sample_rate, const sonar_hpcp_params* params,
+                             double* hpcp /* F x size */, double* energy /* F or NULL */,
+                             double* entropy /* F or NULL */, int32_t device_ptrs);
+/* The contribution table, host only (no context, no GPU), in CSR form: row i (row_start[i] ..
+ * row_start[i+1]) holds what a peak at bin i adds, in the reference's program order: the main
+ * contribution's bins ascending, then harmonic 2's, and so on.  Entry e adds (magnitude * factor[e]) *
+ * window_weight[e] to hpcp[wrapped_bin[e]]; factor is 1, 2 (band preset below split_freq) or
+ * harmonics_strength / h.  Rows of bins outside [min_freq, max_freq], and of bins 0 and K - 1 (never
+ * peaks), are empty.  Call with NULL arrays for *n_entries, then with row_start[K + 1] and three
+ * arrays of *n_entries.  Errors as sonar_hpcp_from_spectrum's (no message: there is no context). */
+int sonar_hpcp_table(int32_t sample_rate, int32_t window_size, int32_t K, const sonar_hpcp_params* params,
+                     int64_t* n_entries, int64_t* row_start /* K + 1 or NULL */,
+                     int32_t* wrapped_bin /* n_entries or NULL */, double* factor, double* window_weight);
+/* The frames of sonar_hpcp on n samples and how it splits them, host only: chunk_frames rows of
+ * window_size / 2 + 1 doubles fill about 64 MiB, n_chunks = ceil(frames / chunk_frames).  Errors are
+ * sonar_fingerprint's (empty, non-positive sizes, too short, a window above its limits). */
+int sonar_hpcp_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* frames, int64_t* chunk_frames,
+                    int64_t* n_chunks);
+/* SpectralAnalyzer.ComputeSTFTWithWindow's magnitude rows (as sonar_fingerprint with
+ * SONAR_FP_MAGNITUDE, float64 PCM, the float64 transform) -> ComputeFromSpectrum per frame, K =
+ * window_size / 2 + 1.  The magnitude rows live in a bounded device scratch, chunk_frames at a time
+ * (sonar_hpcp_plan); chunks partition the frames and share no state.  The window sizes and errors are
+ * sonar_fingerprint's (too short: SONAR_ERR_TOO_SHORT "signal too short for given window size and
+ * hop size"), then sonar_hpcp_from_spectrum's.  hpcp is frames x size. */
+int sonar_hpcp(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t window_size,
+               int32_t hop_size, int32_t window_type, const sonar_hpcp_params* params, double* hpcp,
+               double* energy /* frames or NULL */, double* entropy /* frames or NULL */, int32_t device_ptrs);
 
 /* ---- path B: normalized cross-correlation (float64) --------------------
  * corr has 2L+1 entries, L = max(0, min(max_lag, na-1, nb-1)); metrics[10] =

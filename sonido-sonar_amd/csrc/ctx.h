@@ -83,6 +83,9 @@ struct sonar_ctx {
   // matrix, the ordered sums, the DP fill and the traceback, and the last call's times
   hipEvent_t csim_ev[8] = {};
   double csim_ms[4] = {0.0, 0.0, 0.0, 0.0};
+  // entries of the HPCP contribution tables whose device copies are in bufs under the same names
+  // (hpcp_api.cpp); an entry whose buffer sonar_trim has freed is rebuilt
+  std::map<std::string, int64_t> hpcp_tables;
 };
 
 // Named float64 arrays + scalars.  An array either owns its values (v) or points into a block the
@@ -193,6 +196,8 @@ void ingest_release(sonar_ctx* c);
 // [f_lo, f_hi): only those frames of the whole signal's STFT (device outputs, per-frame kernel)
 int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cfg* cfg, sonar_fp_out* out,
                      bool pcm_dev, int64_t f_lo = 0, int64_t f_hi = -1);
+// sonar_fingerprint's argument checks in its order: SONAR_OK and the frame count, or the code and text
+int fp_check(const sonar_fp_cfg* cfg, int64_t n, bool have_pcm, int64_t* F, std::string* msg);
 // VoiceQualityAnalyzer.AnalyzeVoiceQuality on device-resident float64 samples (voice_api.cpp)
 int voice_quality(sonar_ctx* c, const double* dsig, int64_t n, int32_t sr, sonar_voice_quality_result* out);
 }  // namespace detail

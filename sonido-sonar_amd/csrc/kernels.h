@@ -526,4 +526,33 @@ int launch_chroma_sw_best(const double* tile_best, const int64_t* tile_idx, int6
 int launch_chroma_traceback(const double* M, const uint8_t* tb, int64_t nq, int64_t nr, int dtw, const int64_t* start,
                             int32_t* pq, int32_t* pr, double* ps, int64_t cap, int64_t* plen, hipStream_t s);
 
+// SpectralPeaks.DetectPeaks and HPCP.ComputeFromSpectralPeaks per spectrum row (hpcp_kernels.hip;
+// harmonic/spectral_peaks.go:36-100, chroma/hpcp.go:147-202).  One launch does the peaks of every row
+// and, when hpcp is set, the profile from them; the peak outputs are optional then.
+constexpr int HPCP_MAX_K = 8192;      // bins of a row (candidate bins are kept as 16-bit values)
+constexpr int HPCP_MAX_SIZE = 120;    // bins of the profile: two per lane
+struct HpcpArgs {
+  const double* mag;             // F x K
+  int64_t F;
+  int K;
+  double min_height;
+  int min_dist;                  // min_distance_bins, >= 1 (the greedy runs from 3 on)
+  int P;                         // slots per row: min(max_peaks, (K - 1) / 2)
+  double freq_res;               // float64(sample_rate) / float64(window_size)
+  int32_t* count;                // [F] or null
+  int32_t* bin;                  // [F x P] or null
+  double* pmag;                  // [F x P] or null
+  double* pfreq;                 // [F x P] or null
+  // the contribution table (sonar_hpcp_table) and the profile's switches
+  const int32_t* row_start;      // [K + 1]
+  const int32_t* wbin;
+  const double* factor;
+  const double* weight;
+  int size, non_linear, normalized, max_shifted;
+  double* hpcp;                  // [F x size] or null: peaks only
+  double* energy;                // [F] or null
+  double* entropy;               // [F] or null
+};
+int launch_hpcp(const HpcpArgs& a, hipStream_t s);   // -1: a shape the kernel does not take
+
 }  // namespace sonar

@@ -624,6 +624,10 @@ extern "C" int32_t sonar_fp_kernel_plan(const sonar_fp_cfg* cfg, int64_t n) {
 
 namespace sonar {
 namespace detail {
+int fp_check(const sonar_fp_cfg* cfg, int64_t n, bool have_pcm, int64_t* F, std::string* msg) {
+  return fp_validate(cfg, n, have_pcm, F, msg);
+}
+
 // pcm_dev: pcm is already device memory even though the outputs are host buffers
 // (cfg->device_ptrs == 0) -- the sonar_fingerprint_f64le path (ingest_api.cpp)
 int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cfg* cfg, sonar_fp_out* out,

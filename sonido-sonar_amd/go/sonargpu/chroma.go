@@ -7,7 +7,9 @@ package sonargpu
 // signatures are the reference's.
 //
 // ChromaSequenceSimilarity (algorithms/chroma/chroma_similarity.go) follows at the end of the file,
-// through sonar_chroma_similarity.
+// through sonar_chroma_similarity, then HPCP and SpectralPeaks (algorithms/chroma/hpcp.go,
+// algorithms/harmonic/spectral_peaks.go) through sonar_hpcp_from_spectrum, sonar_hpcp and
+// sonar_spectral_peaks.
 //
 // Written against include/sonar_gpu.h; not compiled here (no Go toolchain in the image).
 
@@ -224,4 +226,219 @@ func (x *Context) ChromaSequenceSimilarity(params ChromaSimilarityParams, query,
 		}
 	}
 	return res, nil
+}
+
+// ---- HPCP and spectral peaks (algorithms/chroma/hpcp.go, algorithms/harmonic/spectral_peaks.go) ----
+//
+// The harmonic pitch class profile through sonar_hpcp_from_spectrum / sonar_hpcp and the peak picker
+// through sonar_spectral_peaks.  MusicFeatureExtractor builds an HPCP beside its two chromagrams
+// (music.go:93); the chord detector and the key estimator call ComputeFromSpectrum frame by frame
+// (tonal/chord_detection.go:529, key_estimation.go:236).  Here a call takes a batch of spectra.
+
+// HPCPParams = chroma.HPCPParams (hpcp.go:11-26).
+type HPCPParams struct {
+	Size              int
+	ReferenceFreq     float64
+	HarmonicsRemoval  bool
+	Normalized        bool
+	WeightType        string // "none", "cosine", "squared_cosine"; anything else is "none", as in Go
+	WindowSize        float64
+	MaxShifted        bool
+	NonLinear         bool
+	BandPreset        bool
+	MinFreq           float64
+	MaxFreq           float64
+	SplitFreq         float64
+	HarmonicsStrength float64
+	MaxHarmonics      int
+}
+
+// HPCPResult = chroma.HPCPResult (hpcp.go:29-36).
+type HPCPResult struct {
+	HPCP       []float64
+	Size       int
+	Resolution float64
+	RefFreq    float64
+	Energy     float64
+	Entropy    float64
+}
+
+// HPCP mirrors chroma.HPCP (:39-51); the contribution table lives in the library, cached in the
+// context per parameter set.
+type HPCP struct {
+	x          *Context
+	params     HPCPParams
+	sampleRate int
+}
+
+// NewHPCP = chroma.NewHPCP (:54-75).
+func (x *Context) NewHPCP(sampleRate int) *HPCP {
+	return x.NewHPCPWithParams(sampleRate, HPCPParams{Size: 12, ReferenceFreq: 440.0, Normalized: true,
+		WeightType: "cosine", WindowSize: 1.0, BandPreset: true, MinFreq: 40.0, MaxFreq: 5000.0, SplitFreq: 500.0,
+		HarmonicsStrength: 1.0})
+}
+
+// NewHPCPWithParams = chroma.NewHPCPWithParams (:78-84).
+func (x *Context) NewHPCPWithParams(sampleRate int, params HPCPParams) *HPCP {
+	return &HPCP{x: x, params: params, sampleRate: sampleRate}
+}
+
+// GetParams / SetParams = HPCP.GetParams / SetParams (:408-416).
+func (h *HPCP) GetParams() HPCPParams        { return h.params }
+func (h *HPCP) SetParams(params HPCPParams) { h.params = params }
+
+func (h *HPCP) cParams() C.sonar_hpcp_params {
+	b := func(v bool) C.int32_t {
+		if v {
+			return 1
+		}
+		return 0
+	}
+	p := h.params
+	wt := C.int32_t(C.SONAR_HPCP_WEIGHT_NONE)
+	switch p.WeightType {
+	case "cosine":
+		wt = C.SONAR_HPCP_WEIGHT_COSINE
+	case "squared_cosine":
+		wt = C.SONAR_HPCP_WEIGHT_SQUARED_COSINE
+	}
+	return C.sonar_hpcp_params{size: C.int32_t(p.Size), harmonics_removal: b(p.HarmonicsRemoval),
+		normalized: b(p.Normalized), weight_type: wt, max_shifted: b(p.MaxShifted), non_linear: b(p.NonLinear),
+		band_preset: b(p.BandPreset), max_harmonics: C.int32_t(p.MaxHarmonics), reference_freq: C.double(p.ReferenceFreq),
+		window_size: C.double(p.WindowSize), min_freq: C.double(p.MinFreq), max_freq: C.double(p.MaxFreq),
+		split_freq: C.double(p.SplitFreq), harmonics_strength: C.double(p.HarmonicsStrength)}
+}
+
+func (h *HPCP) results(flat, energy, entropy []float64, frames int) []HPCPResult {
+	size := h.params.Size
+	out := make([]HPCPResult, frames)
+	for t := range out {
+		out[t] = HPCPResult{HPCP: flat[t*size : (t+1)*size : (t+1)*size], Size: size, Resolution: 12.0 / float64(size),
+			RefFreq: h.params.ReferenceFreq, Energy: energy[t], Entropy: entropy[t]}
+	}
+	return out
+}
+
+// ComputeFromSpectrum = HPCP.ComputeFromSpectrum (:205-221) on every row of a batch of magnitude
+// spectra of one length (the chord detector's rows hold all windowSize bins, the STFT's
+// windowSize/2 + 1).  Size < 0 wraps ErrPanic with Go's makeslice text; parameters the library
+// does not reproduce wrap ErrUnsupported (include/sonar_gpu.h).
+func (h *HPCP) ComputeFromSpectrum(magnitudes [][]float64, windowSize int) ([]HPCPResult, error) {
+	frames := len(magnitudes)
+	if frames == 0 {
+		return nil, nil
+	}
+	bins := len(magnitudes[0])
+	flatMag := make([]float64, frames*bins+1)
+	for t, row := range magnitudes {
+		copy(flatMag[t*bins:(t+1)*bins], row)
+	}
+	size := h.params.Size
+	if size < 0 {
+		size = 0 // the call reports the panic
+	}
+	flat := make([]float64, frames*size+1)
+	energy, entropy := make([]float64, frames), make([]float64, frames)
+	p := h.cParams()
+	if rc := C.sonar_hpcp_from_spectrum(h.x.c, f64p(flatMag), C.int64_t(frames), C.int32_t(bins), C.int32_t(windowSize),
+		C.int32_t(h.sampleRate), &p, f64p(flat), f64p(energy), f64p(entropy), 0); rc != C.SONAR_OK {
+		return nil, h.x.err(rc)
+	}
+	return h.results(flat, energy, entropy, frames), nil
+}
+
+// ComputeFromSignal is SpectralAnalyzer.ComputeSTFTWithWindow(signal, windowSize, hopSize,
+// windowType).Magnitude -> ComputeFromSpectrum per frame in one call (sonar_hpcp): the spectrogram
+// stays on the device, in a bounded scratch.  windowType is a SONAR_WIN_* value.
+func (h *HPCP) ComputeFromSignal(signal []float64, windowSize, hopSize, windowType int) ([]HPCPResult, error) {
+	var frames, chunkFrames, nChunks C.int64_t
+	if rc := C.sonar_hpcp_plan(C.int64_t(len(signal)), C.int32_t(windowSize), C.int32_t(hopSize), &frames, &chunkFrames,
+		&nChunks); rc != C.SONAR_OK {
+		frames = 0 // the call below reports the error in Go's words; it writes nothing
+	}
+	size := h.params.Size
+	if size < 0 {
+		size = 0
+	}
+	flat := make([]float64, int(frames)*size+1)
+	energy, entropy := make([]float64, int(frames)+1), make([]float64, int(frames)+1)
+	p := h.cParams()
+	var pcm *C.double
+	if len(signal) > 0 {
+		pcm = f64p(signal)
+	}
+	if rc := C.sonar_hpcp(h.x.c, pcm, C.int64_t(len(signal)), C.int32_t(h.sampleRate), C.int32_t(windowSize),
+		C.int32_t(hopSize), C.int32_t(windowType), &p, f64p(flat), f64p(energy), f64p(entropy), 0); rc != C.SONAR_OK {
+		return nil, h.x.err(rc)
+	}
+	return h.results(flat, energy, entropy, int(frames)), nil
+}
+
+// ComputeFromSpectrumDevice is ComputeFromSpectrum on device memory: mag (frames x bins float64) and
+// hpcp (frames x Size) are device addresses, energy and entropy (frames each) may be nil.  The profile
+// can go to ChromaSequenceSimilarity's device form as it is, without leaving the device.
+func (h *HPCP) ComputeFromSpectrumDevice(mag unsafe.Pointer, frames, bins, windowSize int, hpcp, energy, entropy unsafe.Pointer) error {
+	p := h.cParams()
+	if rc := C.sonar_hpcp_from_spectrum(h.x.c, (*C.double)(mag), C.int64_t(frames), C.int32_t(bins), C.int32_t(windowSize),
+		C.int32_t(h.sampleRate), &p, (*C.double)(hpcp), (*C.double)(energy), (*C.double)(entropy), 1); rc != C.SONAR_OK {
+		return h.x.err(rc)
+	}
+	return nil
+}
+
+// SpectralPeak = harmonic.SpectralPeak (spectral_peaks.go:9-15).
+type SpectralPeak struct {
+	Frequency float64
+	Magnitude float64
+	Phase     float64
+	BinIndex  int
+	Harmonic  int
+}
+
+// SpectralPeaks mirrors harmonic.SpectralPeaks (:18-23).
+type SpectralPeaks struct {
+	x               *Context
+	sampleRate      int
+	minPeakHeight   float64
+	minPeakDistance float64
+	maxPeaks        int
+}
+
+// NewSpectralPeaks = harmonic.NewSpectralPeaks (:26-33).
+func (x *Context) NewSpectralPeaks(sampleRate int, minPeakHeight, minPeakDistance float64, maxPeaks int) *SpectralPeaks {
+	return &SpectralPeaks{x: x, sampleRate: sampleRate, minPeakHeight: minPeakHeight, minPeakDistance: minPeakDistance,
+		maxPeaks: maxPeaks}
+}
+
+// DetectPeaks = SpectralPeaks.DetectPeaks (:36-100) on every row of a batch of magnitude spectra of
+// one length: per row the peaks by magnitude, descending; equal magnitudes come in ascending bin
+// order (sort.Slice leaves that open).  A negative maxPeaks wraps ErrPanic with Go's slice-bounds text.
+func (sp *SpectralPeaks) DetectPeaks(magnitudeSpectra [][]float64, windowSize int) ([][]SpectralPeak, error) {
+	frames := len(magnitudeSpectra)
+	if frames == 0 {
+		return nil, nil
+	}
+	bins := len(magnitudeSpectra[0])
+	flatMag := make([]float64, frames*bins+1)
+	for t, row := range magnitudeSpectra {
+		copy(flatMag[t*bins:(t+1)*bins], row)
+	}
+	width := int(C.sonar_spectral_peaks_width(C.int64_t(bins), C.int64_t(sp.maxPeaks)))
+	count := make([]int32, frames)
+	bin := make([]int32, frames*width+1)
+	mag, freq := make([]float64, frames*width+1), make([]float64, frames*width+1)
+	if rc := C.sonar_spectral_peaks(sp.x.c, f64p(flatMag), C.int64_t(frames), C.int32_t(bins), C.int32_t(windowSize),
+		C.int32_t(sp.sampleRate), C.double(sp.minPeakHeight), C.double(sp.minPeakDistance), C.int32_t(sp.maxPeaks),
+		(*C.int32_t)(unsafe.Pointer(&count[0])), (*C.int32_t)(unsafe.Pointer(&bin[0])), f64p(mag), f64p(freq), 0); rc != C.SONAR_OK {
+		return nil, sp.x.err(rc)
+	}
+	out := make([][]SpectralPeak, frames)
+	for t := range out {
+		out[t] = make([]SpectralPeak, int(count[t]))
+		for r := range out[t] {
+			o := t*width + r
+			out[t][r] = SpectralPeak{Frequency: freq[o], Magnitude: mag[o], Phase: 0.0, BinIndex: int(bin[o]), Harmonic: -1}
+		}
+	}
+	return out, nil
 }

@@ -10,6 +10,10 @@ same for every type, method and constructor, ``Context.dtw`` ~ DTWAlignment.Alig
 ``Context.chroma_cqt`` ~ NewChromaCQT(...).ComputeChroma (``chroma_cqt_plan``: its sizes, host only),
 ``Context.chroma_similarity`` ~ ChromaSequenceSimilarity.ComputeSimilarity (``chroma_frame_matrix``: its
 frame distances / similarities, ``chroma_similarity_plan``: its integer side, host only),
+``Context.spectral_peaks`` ~ SpectralPeaks.DetectPeaks per spectrum row, ``Context.hpcp_from_spectrum`` ~
+HPCP.ComputeFromSpectrum per row and ``Context.hpcp`` ~ the same over the STFT magnitudes of a signal
+(``hpcp_params``: NewHPCP's defaults, ``hpcp_table``: the per-bin contribution table, ``hpcp_plan``: the
+frame count and chunks, host only),
 ``Context.generate_fingerprint`` ~ FingerprintGenerator.GenerateFingerprint,
 ``Context.align_features`` ~ AlignmentExtractor.ExtractAlignmentFeatures.
 
@@ -42,6 +46,12 @@ from ._abi import (  # noqa: F401
     fp_kernel_plan,
     chroma_cqt_plan,
     chroma_similarity_plan,
+    HpcpParams,
+    HPCP_WEIGHTS,
+    hpcp_params,
+    hpcp_table,
+    hpcp_plan,
+    spectral_peaks_width,
     CHROMA_SIM_METHODS,
     CHROMA_DIST_METRICS,
     PLAN_NONE,

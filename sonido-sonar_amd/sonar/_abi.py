@@ -64,6 +64,17 @@ class FpConfig(C.Structure):
                 ("out_dtype", C.c_int32), ("device_ptrs", C.c_int32)]
 
 
+class HpcpParams(C.Structure):
+    """sonar_hpcp_params (HPCPParams, algorithms/chroma/hpcp.go:11-26)."""
+    _fields_ = [(n, C.c_int32) for n in ("size", "harmonics_removal", "normalized", "weight_type", "max_shifted",
+                                         "non_linear", "band_preset", "max_harmonics")] + \
+               [(n, C.c_double) for n in ("reference_freq", "window_size", "min_freq", "max_freq", "split_freq",
+                                          "harmonics_strength")]
+
+
+HPCP_WEIGHTS = {"none": 0, "cosine": 1, "squared_cosine": 2}
+
+
 class FpOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ["mfcc", "magnitude", "centroid", "rolloff", "bandwidth", "flatness",
                                           "crest", "slope", "flux", "low_ratio", "high_ratio", "zcr", "energy",
@@ -236,6 +247,18 @@ def lib():
     L.sonar_chroma_similarity_plan.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                _i64p, _i64p, _i64p, _i64p, _i64p]
     L.sonar_chroma_similarity_last_timing.argtypes = [_vp, C.POINTER(C.c_double)]
+    L.sonar_spectral_peaks_width.argtypes = [C.c_int64, C.c_int64]
+    L.sonar_spectral_peaks_width.restype = C.c_int64
+    L.sonar_spectral_peaks.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                       C.c_int32, _vp, _vp, _vp, _vp, C.c_int32]
+    L.sonar_hpcp_params_default.argtypes = [C.POINTER(HpcpParams)]
+    L.sonar_hpcp_params_default.restype = None
+    L.sonar_hpcp_from_spectrum.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HpcpParams),
+                                           _vp, _vp, _vp, C.c_int32]
+    L.sonar_hpcp_table.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(HpcpParams), _i64p, _vp, _vp, _vp, _vp]
+    L.sonar_hpcp_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p, _i64p]
+    L.sonar_hpcp.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HpcpParams),
+                             _vp, _vp, _vp, C.c_int32]
     L.sonar_ncc.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, _vp, C.c_int32]
@@ -441,6 +464,61 @@ def chroma_similarity_plan(method, nq, nr, dim=12, oti_radius=10, dtw_band_radiu
         raise SonarError(rc, "sonar_chroma_similarity_plan: negative frame count or dim < 1")
     return dict(zip(("sample_step", "sampled_pairs", "oti_cells", "dtw_skipped_columns", "scratch_bytes"),
                     [x.value for x in v]))
+
+
+def hpcp_params(**kw):
+    """sonar_hpcp_params with NewHPCP's defaults (sonar_hpcp_params_default), fields overridden by
+    keyword; weight_type takes Go's string ("none", "cosine", "squared_cosine"; any other string is
+    "none", as in Go) or the enum value."""
+    p = HpcpParams()
+    lib().sonar_hpcp_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "weight_type" and isinstance(v, str):
+            v = HPCP_WEIGHTS.get(v, 0)
+        setattr(p, k, v)
+    return p
+
+
+_HPCP_ERRORS = {ERR_PANIC: "runtime error: makeslice: len out of range",
+                ERR_UNSUPPORTED: "HPCP: parameters the library does not reproduce (include/sonar_gpu.h)",
+                ERR_INVALID: "HPCP: invalid argument"}
+_HPCP_PLAN_ERRORS = {ERR_EMPTY: "empty signal", ERR_INVALID: "window size and hop size must be positive",
+                     ERR_TOO_SHORT: "signal too short for given window size and hop size",
+                     ERR_UNSUPPORTED: "window size above the generic STFT path's limit"}
+
+
+def spectral_peaks_width(K, max_peaks):
+    """sonar_spectral_peaks_width: slots per row of spectral_peaks, min(max_peaks, max((K - 1) / 2, 0))."""
+    return int(lib().sonar_spectral_peaks_width(int(K), int(max_peaks)))
+
+
+def hpcp_table(sample_rate, window_size, K, params=None):
+    """sonar_hpcp_table (host only): the CSR contribution table of NewHPCPWithParams(sample_rate, params)
+    for rows of K bins at window_size -> dict of row_start (int64, K + 1), wrapped_bin (int32), factor,
+    window_weight."""
+    L = lib()
+    p = params if params is not None else hpcp_params()
+    n = C.c_int64()
+    rc = L.sonar_hpcp_table(int(sample_rate), int(window_size), int(K), C.byref(p), C.byref(n), None, None, None, None)
+    if rc != OK:
+        raise SonarError(rc, _HPCP_ERRORS.get(rc, "sonar_hpcp_table"))
+    rs = np.zeros(int(K) + 1, np.int64)
+    wb, fac, ww = np.zeros(n.value, np.int32), np.zeros(n.value), np.zeros(n.value)
+    rc = L.sonar_hpcp_table(int(sample_rate), int(window_size), int(K), C.byref(p), C.byref(n), _ptr(rs), _ptr(wb),
+                            _ptr(fac), _ptr(ww))
+    if rc != OK:
+        raise SonarError(rc, _HPCP_ERRORS.get(rc, "sonar_hpcp_table"))
+    return {"row_start": rs, "wrapped_bin": wb, "factor": fac, "window_weight": ww}
+
+
+def hpcp_plan(n, window_size, hop_size):
+    """sonar_hpcp_plan (host only): how Context.hpcp splits its frames -> dict of frames, chunk_frames,
+    n_chunks."""
+    v = [C.c_int64() for _ in range(3)]
+    rc = lib().sonar_hpcp_plan(int(n), int(window_size), int(hop_size), *[C.byref(x) for x in v])
+    if rc != OK:
+        raise SonarError(rc, _HPCP_PLAN_ERRORS.get(rc, "sonar_hpcp_plan"))
+    return dict(zip(("frames", "chunk_frames", "n_chunks"), [x.value for x in v]))
 
 
 def multi_shard(n, W, H, n_shards, shard):
@@ -808,6 +886,78 @@ class Context:
         self._check(self._L.sonar_chroma_cqt(self._h, pcm_ptr, int(n), int(hop), int(sample_rate), float(min_freq),
                                              float(max_freq), int(bins_per_octave), float(q_factor),
                                              float(tuning_freq), chroma_ptr, cqt_ptr, 1))
+
+    def spectral_peaks(self, mag, window_size, sample_rate, min_height=0.00001, min_distance_hz=20.0, max_peaks=60):
+        """NewSpectralPeaks(sample_rate, min_height, min_distance_hz, max_peaks).DetectPeaks(row,
+        window_size) on every row of mag (F x K) (sonar_spectral_peaks; the defaults are
+        HPCP.ComputeFromSpectrum's) -> dict of count (F), bin, magnitude, frequency (F x P, sorted by
+        magnitude descending then bin ascending, zeros past count)."""
+        mag = _f64(mag)
+        mag = mag[None, :] if mag.ndim == 1 else mag
+        F, K = mag.shape
+        P = max(spectral_peaks_width(K, max_peaks), 0)
+        count, bins = np.zeros(F, np.int32), np.zeros((F, P), np.int32)
+        pm, pf = np.zeros((F, P)), np.zeros((F, P))
+        self._check(self._L.sonar_spectral_peaks(self._h, _ptr(mag) if mag.size else None, F, K, int(window_size),
+                                                 int(sample_rate), float(min_height), float(min_distance_hz),
+                                                 int(max_peaks), _ptr(count) if F else None, _ptr(bins), _ptr(pm),
+                                                 _ptr(pf), 0))
+        return {"count": count, "bin": bins, "magnitude": pm, "frequency": pf}
+
+    def spectral_peaks_device(self, mag_ptr, F, K, window_size, sample_rate, count_ptr, bin_ptr, magnitude_ptr,
+                              frequency_ptr=None, min_height=0.00001, min_distance_hz=20.0, max_peaks=60):
+        """spectral_peaks on device memory (device_ptrs = 1): every array is a device address."""
+        self._check(self._L.sonar_spectral_peaks(self._h, mag_ptr, int(F), int(K), int(window_size), int(sample_rate),
+                                                 float(min_height), float(min_distance_hz), int(max_peaks), count_ptr,
+                                                 bin_ptr, magnitude_ptr, frequency_ptr, 1))
+
+    def hpcp_from_spectrum(self, mag, window_size, sample_rate, params=None):
+        """NewHPCPWithParams(sample_rate, params).ComputeFromSpectrum(row, window_size) on every row of mag
+        (F x K) (sonar_hpcp_from_spectrum; params: hpcp_params(...), default NewHPCP's) -> dict of hpcp
+        (F x size), energy, entropy (F)."""
+        p = params if params is not None else hpcp_params()
+        mag = _f64(mag)
+        mag = mag[None, :] if mag.ndim == 1 else mag
+        F, K = mag.shape
+        out, e, h = np.zeros((F, max(p.size, 0))), np.zeros(F), np.zeros(F)
+        self._check(self._L.sonar_hpcp_from_spectrum(self._h, _ptr(mag) if mag.size else None, F, K, int(window_size),
+                                                     int(sample_rate), C.byref(p), _ptr(out), _ptr(e), _ptr(h), 0))
+        return {"hpcp": out, "energy": e, "entropy": h}
+
+    def hpcp_from_spectrum_device(self, mag_ptr, F, K, window_size, sample_rate, hpcp_ptr, params=None,
+                                  energy_ptr=None, entropy_ptr=None):
+        """hpcp_from_spectrum on device memory (device_ptrs = 1): mag (F x K), hpcp (F x size) and the
+        optional energy and entropy (F) are device addresses; the profile can go to
+        chroma_similarity_device as it is."""
+        p = params if params is not None else hpcp_params()
+        self._check(self._L.sonar_hpcp_from_spectrum(self._h, mag_ptr, int(F), int(K), int(window_size),
+                                                     int(sample_rate), C.byref(p), hpcp_ptr, energy_ptr, entropy_ptr, 1))
+
+    def hpcp(self, pcm, sample_rate, window_size=2048, hop_size=512, window_type="hann", params=None):
+        """SpectralAnalyzer.ComputeSTFTWithWindow(pcm, window_size, hop_size, window_type) magnitudes ->
+        HPCP.ComputeFromSpectrum per frame (sonar_hpcp: float64 PCM, the float64 transform, the rows in
+        a bounded device scratch, hpcp_plan's chunks) -> dict of hpcp (frames x size), energy, entropy."""
+        p = params if params is not None else hpcp_params()
+        pcm = _f64(pcm)
+        n = len(pcm)
+        wt = WINDOWS[window_type] if isinstance(window_type, str) else int(window_type)
+        v = [C.c_int64() for _ in range(3)]
+        F = 0
+        if self._L.sonar_hpcp_plan(n, int(window_size), int(hop_size), *[C.byref(x) for x in v]) == OK:
+            F = v[0].value                                  # otherwise the call below reports the error
+        out, e, h = np.zeros((F, max(p.size, 0))), np.zeros(F), np.zeros(F)
+        self._check(self._L.sonar_hpcp(self._h, _ptr(pcm) if n else None, n, int(sample_rate), int(window_size),
+                                       int(hop_size), wt, C.byref(p), _ptr(out), _ptr(e), _ptr(h), 0))
+        return {"hpcp": out, "energy": e, "entropy": h}
+
+    def hpcp_device(self, pcm_ptr, n, sample_rate, hpcp_ptr, window_size=2048, hop_size=512, window_type="hann",
+                    params=None, energy_ptr=None, entropy_ptr=None):
+        """hpcp on device memory (device_ptrs = 1): pcm (n doubles), hpcp (frames x size) and the optional
+        energy and entropy are device addresses; frames is hpcp_plan's."""
+        p = params if params is not None else hpcp_params()
+        wt = WINDOWS[window_type] if isinstance(window_type, str) else int(window_type)
+        self._check(self._L.sonar_hpcp(self._h, pcm_ptr, int(n), int(sample_rate), int(window_size), int(hop_size), wt,
+                                       C.byref(p), hpcp_ptr, energy_ptr, entropy_ptr, 1))
 
     def music_alignment_features(self, pcm, sample_rate, stft_window=1024, stft_hop=256, feature_window=1024,
                                  feature_hop=256):
