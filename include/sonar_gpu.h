@@ -36,6 +36,11 @@
  *   sonar_hpcp_table           <- frequencyToPitchClass, addPeakContribution, computeWindowWeight and
  *                                 addHarmonicContributions per FFT bin (hpcp.go:224-321)
  *   sonar_hpcp_plan            <- the frame count and the chunks sonar_hpcp works in
+ *   sonar_key_frames           <- KeyEstimator.EstimateKey / EstimateKeyFromHPCP per chroma row,
+ *                                 KeyEstimationBatch.ProcessBatch (algorithms/tonal/key_estimation.go:196-247, 911)
+ *   sonar_key_sequence         <- KeyEstimator.EstimateKeySequence (key_estimation.go:250-270)
+ *   sonar_key_batch            <- KeyEstimationBatch.ProcessBatch / GetGlobalKey / GetKeyProgression (:896-1005)
+ *   sonar_key_transition       <- AnalyzeKeyTransition (:843-894)
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
  *   sonar_xcorr_params         <- CrossCorrelation.Compute for every type, method and constructor
@@ -535,6 +540,114 @@ int sonar_hpcp_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* f
 int sonar_hpcp(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t window_size,
                int32_t hop_size, int32_t window_type, const sonar_hpcp_params* params, double* hpcp,
                double* energy /* frames or NULL */, double* entropy /* frames or NULL */, int32_t device_ptrs);
+
+/* ---- key estimation over a chromagram (float64) ----------------------------
+ * KeyEstimator (algorithms/tonal/key_estimation.go) on F rows of dim chroma values, for example the
+ * profile sonar_hpcp leaves on the device.  The entries are stateless: keyHistory, which the
+ * reference grows on every internal EstimateKey, is the last 20 first candidates of the per-frame
+ * output and is left to the caller.
+ *
+ * EstimateKey (:196-233) of one row:
+ *   preprocessChroma (:273-297): when dim != hpcp_size, resizeChromaVector (:464-485): entry i takes
+ *   row[int(float64(i) * (float64(dim) / float64(hpcp_size)))] when that index is < dim, else 0;
+ *   normalize_chroma: divided by sqrt(sum x^2) only when sum x^2 >= 1e-10 (common/normalization.go:
+ *   113-134); remove_mean: minus the mean (the in-order sum / n); binary_mode: > mean as 1.0 / 0.0.
+ *   estimateKeyProfile (:300-370): scores[mode * 12 + key] = stats.PearsonCorrelationFunc(row, shifted)
+ *   (stats/distance.go:111-145), shifted[i] = profile[(i + key) % 12], so key k's template has its
+ *   tonic at pitch class (12 - k) % 12; 0 when either centred sum of squares is 0,
+ *   and every score is 0 when hpcp_size != 12 (correlateWithProfile's length test, F44).  The 24
+ *   candidates, created in the order C major, C minor, C# major, ..., are sorted by score, descending;
+ *   sort.Slice leaves the order of equal scores open, here they stay in creation order (F45); the first
+ *   min(max_candidates, 24) are kept, as codes key * 2 + mode.  key, mode and strength are the first
+ *   candidate's, clarity = (s0 - s1) / s0 over the descending scores when s0 > 0, else 0; ambiguity =
+ *   the entropy (math.Log2) of the positive scores over their sum, / log2(24), 0 when nothing is
+ *   positive; tonality = 1 - computeUniformity(processed row) (chroma/chroma_vector.go:385-408).
+ *   postProcessResult (:675-686): confidence = the first candidate's score, or 0 with known = 0 ("Unknown")
+ *   when it is < min_confidence; key, mode, strength and the candidates keep their values.
+ *   profile outside 0..6 is Krumhansl (:301-305).  There is no method field: every method runs the
+ *   profile correlation (F43).
+ * Go's panics are SONAR_ERR_PANIC with Go's text, tested in Go's order, only when F > 0 (no row,
+ * no EstimateKey): hpcp_size < 0 "runtime error: makeslice:
+ * len out of range"; max_candidates < 0 "runtime error: slice bounds out of range [:-1]" (the value);
+ * max_candidates == 0, and then hpcp_size == 0 (ComputeStats' values[0]), "runtime error: index out of
+ * range [0] with length 0".  dim == 0 with a positive hpcp_size is legal: rows of zeros.
+ * Not reproduced (SONAR_ERR_UNSUPPORTED): dim or hpcp_size above 120; F above 2^31 - 1; any non-finite
+ * chroma value that is read (a NaN score makes sort.Slice's order undefined; outputs are then
+ * unspecified).
+ * With device_ptrs = 1 the chromagram and every output, the single values included, are device
+ * addresses; the call returns after the stream has drained either way.  Every output may be NULL and
+ * then costs nothing. */
+#define SONAR_KEY_PROFILE_KRUMHANSL 0
+#define SONAR_KEY_PROFILE_TEMPERLEY 1
+#define SONAR_KEY_PROFILE_SHAATH 2
+#define SONAR_KEY_PROFILE_EDMA 3
+#define SONAR_KEY_PROFILE_BGATE 4
+#define SONAR_KEY_PROFILE_DIATONIC 5
+#define SONAR_KEY_PROFILE_TONIC_TRIAD 6
+/* The fields of KeyEstimationParams (:88-113) the reference reads. */
+typedef struct sonar_key_params {
+  int32_t profile;           /* Profile */
+  int32_t hpcp_size;         /* HPCPSize */
+  int32_t normalize_chroma;  /* NormalizeChroma */
+  int32_t remove_mean;       /* RemoveMean */
+  int32_t binary_mode;       /* BinaryMode */
+  int32_t max_candidates;    /* MaxCandidates */
+  double min_confidence;     /* MinConfidence */
+} sonar_key_params;
+/* NewKeyEstimator's values (:141-166): Krumhansl, 12, normalized, mean kept, not binary, 5, 0.5. */
+void sonar_key_params_default(sonar_key_params* p);
+
+/* EstimateKey per row; also KeyEstimationBatch.ProcessBatch (:911-920) and EstimateKeyFromHPCP
+ * (:236-247) per HPCP row.  key, mode, known, confidence, strength, clarity, ambiguity, tonality: F
+ * each.  F == 0 -> SONAR_OK, nothing is read or written. */
+int sonar_key_frames(sonar_ctx* ctx, const double* chroma /* F x dim */, int64_t F, int32_t dim,
+                     const sonar_key_params* params, int32_t* key, int32_t* mode, int32_t* known,
+                     double* confidence, double* strength, double* clarity, double* ambiguity, double* tonality,
+                     double* scores /* F x 24 */, int32_t* candidates /* F x min(max_candidates, 24) */,
+                     double* processed /* F x hpcp_size */, int32_t device_ptrs);
+/* EstimateKeySequence (:250-270).  The single result is EstimateKey of computeAverageChroma (:575-596:
+ * per bin the sum over the frames in frame order, / F): one value per field, scores[24],
+ * processed[hpcp_size].  stability (analyzeTemporalStability :598-622): 0 below 3 frames, else the share
+ * of frames whose code key * 2 + mode equals the most frequent one (findMode iterates a map; here the
+ * lowest code among the most frequent wins, F45); a frame below min_confidence still votes (F46).
+ * modulations (detectModulations :624-655; capacity max(F - 20, 0), ascending, *n_modulations of them):
+ * nothing at 20 frames or fewer; for i = 10 .. F - 11 the in-order mean of the 10 rows [i - 5, i + 5) is
+ * estimated, and i is reported when its code differs from position i - 1's and its thresholded
+ * confidence is > 0.7; position 10 has no predecessor, so nothing is reported below 22 frames (F47).
+ * F == 0 -> SONAR_OK, all zeros. */
+int sonar_key_sequence(sonar_ctx* ctx, const double* chroma /* F x dim */, int64_t F, int32_t dim,
+                       const sonar_key_params* params, int32_t* key, int32_t* mode, int32_t* known,
+                       double* confidence, double* strength, double* clarity, double* ambiguity, double* tonality,
+                       double* scores /* 24 */, double* processed /* hpcp_size */, double* stability,
+                       int32_t* modulations /* max(F - 20, 0) */, int64_t* n_modulations, int32_t device_ptrs);
+#define SONAR_KEY_TRANSITION_SAME_KEY 0
+#define SONAR_KEY_TRANSITION_PARALLEL 1
+#define SONAR_KEY_TRANSITION_RELATIVE 2
+#define SONAR_KEY_TRANSITION_DOMINANT 3
+#define SONAR_KEY_TRANSITION_SUBDOMINANT 4
+#define SONAR_KEY_TRANSITION_DISTANT 5
+/* KeyEstimationBatch (:896-1005): ProcessBatch's per-frame outputs as sonar_key_frames', then
+ * GetGlobalKey (:923-959): in frame order every frame with confidence > 0.5 adds its confidence to its
+ * key's vote (votes[24], by code) and to a total; the largest vote wins (the reference iterates a map;
+ * here the lowest code among equal votes, F45); *global_code = its code, -1 when nothing voted (Go's
+ * empty name); *global_confidence = best / total (0 / 0 = NaN then); *global_strength = best / F.
+ * GetKeyProgression (:962-989): a record for every frame i >= 1 whose confidence and its predecessor's
+ * are both > 0.5, the same key included: t_frame = i, t_from / t_to the two codes, t_confidence their
+ * mean, t_type AnalyzeKeyTransition's type; capacity max(F - 1, 0), ascending, *n_transitions of them.
+ * F == 0 -> SONAR_OK: code -1, confidence 0, strength 0, no votes, no transitions. */
+int sonar_key_batch(sonar_ctx* ctx, const double* chroma /* F x dim */, int64_t F, int32_t dim,
+                    const sonar_key_params* params, int32_t* key, int32_t* mode, int32_t* known,
+                    double* confidence, double* strength, double* clarity, double* ambiguity, double* tonality,
+                    double* scores, int32_t* candidates, double* processed, int32_t* global_code,
+                    double* global_confidence, double* global_strength, double* votes /* 24 */,
+                    int32_t* t_frame, int32_t* t_from, int32_t* t_to, double* t_confidence, int32_t* t_type,
+                    int64_t* n_transitions, int32_t device_ptrs);
+/* AnalyzeKeyTransition (:843-894), host only: *type (same key, then parallel, relative by
+ * GetRelativeKey, dominant (+7), subdominant (-7), else distant), *semitone_distance = (to - from + 12)
+ * % 12, *fifths_distance = 0 (same, parallel), 1 (relative, dominant, subdominant), else
+ * min(distance, 12 - distance); *strength = 1 / (1 + fifths_distance).  Any output may be NULL. */
+int sonar_key_transition(int32_t from_key, int32_t from_mode, int32_t to_key, int32_t to_mode, int32_t* type,
+                         int32_t* semitone_distance, int32_t* fifths_distance, double* strength);
 
 /* ---- path B: normalized cross-correlation (float64) --------------------
  * corr has 2L+1 entries, L = max(0, min(max_lag, na-1, nb-1)); metrics[10] =

@@ -555,4 +555,54 @@ struct HpcpArgs {
 };
 int launch_hpcp(const HpcpArgs& a, hipStream_t s);   // -1: a shape the kernel does not take
 
+// KeyEstimator over a chromagram (key_kernels.hip; algorithms/tonal/key_estimation.go).
+// AnalyzeKeyTransition's transition type (:843-872), shared by sonar_key_transition and the
+// transition records of sonar_key_batch.  Go's % keeps the dividend's sign, as C's does.
+__host__ __device__ inline int key_transition_type(int fk, int fm, int tk, int tm) {
+  if (fk == tk && fm == tm) return SONAR_KEY_TRANSITION_SAME_KEY;
+  if (fk == tk) return SONAR_KEY_TRANSITION_PARALLEL;
+  const int rel_key = fm == 0 ? (fk - 3 + 12) % 12 : (fk + 3) % 12;    // GetRelativeKey (:776-786)
+  const int rel_mode = fm == 0 ? 1 : 0;
+  if (tk == rel_key && tm == rel_mode) return SONAR_KEY_TRANSITION_RELATIVE;
+  if (tk == (fk + 7) % 12 && tm == fm) return SONAR_KEY_TRANSITION_DOMINANT;            // :798-801
+  if (tk == (fk - 7 + 12) % 12 && tm == fm) return SONAR_KEY_TRANSITION_SUBDOMINANT;    // :804-807
+  return SONAR_KEY_TRANSITION_DISTANT;
+}
+constexpr int KEY_MAX_SIZE = HPCP_MAX_SIZE;   // dim and hpcp_size: a lane's row lives in LDS
+constexpr int KEY_TILE_FRAMES = 1024;         // frames per round of the vote chain
+constexpr int KEY_TILE_ELEMS = 3840;          // values per round of the column sums: 3840 / dim frames
+constexpr int KEY_TAB_ROW = 13;               // per (mode, key): diffB[12], sumSqB
+// EstimateKey per row.  window == 0: row f is chroma row f.  window == 10: row f is
+// detectModulations' position f + 10, the in-order mean of chroma rows f + 5 .. f + 14.
+struct KeyArgs {
+  const double* chroma;          // rows of dim values
+  int64_t F;                     // rows to estimate
+  int dim, hs, window;
+  const int32_t* ridx;           // [hs] resizeChromaVector's source index, -1: stays 0; null when dim == hs
+  const double* tab;             // [24 x KEY_TAB_ROW], index mode * 12 + key; read when hs == 12
+  int normalize, remove_mean, binary, ncand;
+  double min_conf, log2_24;
+  int32_t *key, *mode, *known, *code, *cand;   // each [F] (cand [F x ncand]) or null
+  double *conf, *strength, *clarity, *ambiguity, *tonality, *scores, *processed;
+  int32_t* nonfinite;            // set to 1 when a staged value is not finite
+};
+int launch_key_rows(const KeyArgs& a, hipStream_t s);   // -1: a shape the kernel does not take
+// avg[k] = (the sum of column k over the F rows, in row order) / F
+int launch_key_colsum(const double* chroma, int64_t F, int dim, double* avg, hipStream_t s);
+// analyzeTemporalStability's tail: the share of the most frequent code (the lowest among equals); 0 below 3 rows
+int launch_key_stability(const int32_t* code, int64_t F, double* stability, hipStream_t s);
+// GetGlobalKey: votes in frame order; any of the four outputs may be null
+int launch_key_votes(const int32_t* code, const double* conf, int64_t F, double* votes, int32_t* gcode, double* gconf,
+                     double* gstrength, hipStream_t s);
+struct KeyCompactArgs {
+  const int32_t* code;
+  const double* conf;
+  int64_t n;                     // entries of code / conf
+  int transitions;               // 0: modulations (entry e is position e + 10); 1: GetKeyProgression
+  int32_t *frame, *from, *to, *type;   // frame: the modulation positions or the transition frames; any may be null
+  double* tconf;
+  int64_t* count;                // or null
+};
+int launch_key_compact(const KeyCompactArgs& a, hipStream_t s);
+
 }  // namespace sonar

@@ -14,6 +14,10 @@ frame distances / similarities, ``chroma_similarity_plan``: its integer side, ho
 HPCP.ComputeFromSpectrum per row and ``Context.hpcp`` ~ the same over the STFT magnitudes of a signal
 (``hpcp_params``: NewHPCP's defaults, ``hpcp_table``: the per-bin contribution table, ``hpcp_plan``: the
 frame count and chunks, host only),
+``Context.key_frames`` ~ KeyEstimator.EstimateKey per chroma row (also ProcessBatch and EstimateKeyFromHPCP),
+``Context.key_sequence`` ~ EstimateKeySequence and ``Context.key_batch`` ~ KeyEstimationBatch's ProcessBatch,
+GetGlobalKey and GetKeyProgression (``key_params``: NewKeyEstimator's defaults, ``key_transition``:
+AnalyzeKeyTransition, host only, ``key_name``: getKeyName of a code),
 ``Context.generate_fingerprint`` ~ FingerprintGenerator.GenerateFingerprint,
 ``Context.align_features`` ~ AlignmentExtractor.ExtractAlignmentFeatures.
 
@@ -52,6 +56,14 @@ from ._abi import (  # noqa: F401
     hpcp_table,
     hpcp_plan,
     spectral_peaks_width,
+    KeyParams,
+    KEY_PROFILES,
+    KEY_TRANSITIONS,
+    KEY_NAMES,
+    KEY_FRAME_FIELDS,
+    key_params,
+    key_name,
+    key_transition,
     CHROMA_SIM_METHODS,
     CHROMA_DIST_METRICS,
     PLAN_NONE,

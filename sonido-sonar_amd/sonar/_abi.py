@@ -75,6 +75,20 @@ class HpcpParams(C.Structure):
 HPCP_WEIGHTS = {"none": 0, "cosine": 1, "squared_cosine": 2}
 
 
+class KeyParams(C.Structure):
+    """sonar_key_params: the fields of KeyEstimationParams the reference reads (key_estimation.go:88-113)."""
+    _fields_ = [(n, C.c_int32) for n in ("profile", "hpcp_size", "normalize_chroma", "remove_mean", "binary_mode",
+                                         "max_candidates")] + [("min_confidence", C.c_double)]
+
+
+# KeyProfile (SONAR_KEY_PROFILE_*), the transition types (SONAR_KEY_TRANSITION_*) and getKeyName's names
+KEY_PROFILES = {"krumhansl": 0, "temperley": 1, "shaath": 2, "edma": 3, "bgate": 4, "diatonic": 5, "tonic_triad": 6}
+KEY_TRANSITIONS = ["same_key", "parallel", "relative", "dominant", "subdominant", "distant"]
+KEY_NAMES = ["C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B"]
+KEY_FRAME_FIELDS = ("key", "mode", "known", "confidence", "strength", "clarity", "ambiguity", "tonality", "scores",
+                    "candidates", "processed")
+
+
 class FpOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ["mfcc", "magnitude", "centroid", "rolloff", "bandwidth", "flatness",
                                           "crest", "slope", "flux", "low_ratio", "high_ratio", "zcr", "energy",
@@ -259,6 +273,13 @@ def lib():
     L.sonar_hpcp_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p, _i64p]
     L.sonar_hpcp.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HpcpParams),
                              _vp, _vp, _vp, C.c_int32]
+    L.sonar_key_params_default.argtypes = [C.POINTER(KeyParams)]
+    L.sonar_key_params_default.restype = None
+    _key = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(KeyParams)]
+    L.sonar_key_frames.argtypes = _key + [_vp] * 11 + [C.c_int32]
+    L.sonar_key_sequence.argtypes = _key + [_vp] * 13 + [C.c_int32]
+    L.sonar_key_batch.argtypes = _key + [_vp] * 21 + [C.c_int32]
+    L.sonar_key_transition.argtypes = [C.c_int32] * 4 + [_i32p, _i32p, _i32p, _d]
     L.sonar_ncc.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, _vp, C.c_int32]
@@ -485,6 +506,46 @@ _HPCP_ERRORS = {ERR_PANIC: "runtime error: makeslice: len out of range",
 _HPCP_PLAN_ERRORS = {ERR_EMPTY: "empty signal", ERR_INVALID: "window size and hop size must be positive",
                      ERR_TOO_SHORT: "signal too short for given window size and hop size",
                      ERR_UNSUPPORTED: "window size above the generic STFT path's limit"}
+
+
+def key_params(**kw):
+    """sonar_key_params with NewKeyEstimator's defaults (sonar_key_params_default), fields overridden by
+    keyword; profile takes a name of KEY_PROFILES or the enum value."""
+    p = KeyParams()
+    lib().sonar_key_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "profile" and isinstance(v, str):
+            v = KEY_PROFILES[v]
+        setattr(p, k, v)
+    return p
+
+
+def key_name(code):
+    """getKeyName of a code key * 2 + mode ("C major", ...); -1 is GetGlobalKey's empty name."""
+    return "" if code < 0 else KEY_NAMES[(code >> 1) % 12] + (" minor" if code & 1 else " major")
+
+
+def key_transition(from_key, from_mode, to_key, to_mode):
+    """AnalyzeKeyTransition (sonar_key_transition, host only) -> dict of transition_type (a name of
+    KEY_TRANSITIONS), type, semitone_distance, fifths_distance, transition_strength."""
+    t, sd, fd, st = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+    lib().sonar_key_transition(int(from_key), int(from_mode), int(to_key), int(to_mode), C.byref(t), C.byref(sd),
+                               C.byref(fd), C.byref(st))
+    return {"transition_type": KEY_TRANSITIONS[t.value], "type": t.value, "semitone_distance": sd.value,
+            "fifths_distance": fd.value, "transition_strength": st.value}
+
+
+def _key_frame_arrays(F, p, skip=()):
+    """numpy outputs of the per-frame fields (None for the names in skip), in the C argument order."""
+    nc, hs = min(max(p.max_candidates, 0), 24), max(p.hpcp_size, 0)
+    shapes = {"key": ((F,), np.int32), "mode": ((F,), np.int32), "known": ((F,), np.int32),
+              "scores": ((F, 24), np.float64), "candidates": ((F, nc), np.int32), "processed": ((F, hs), np.float64)}
+    return {n: None if n in skip else np.zeros(*shapes.get(n, ((F,), np.float64))) for n in KEY_FRAME_FIELDS}
+
+
+def _key_rows(chroma):
+    chroma = _f64(chroma)
+    return chroma[None, :] if chroma.ndim == 1 else chroma
 
 
 def spectral_peaks_width(K, max_peaks):
@@ -958,6 +1019,93 @@ class Context:
         wt = WINDOWS[window_type] if isinstance(window_type, str) else int(window_type)
         self._check(self._L.sonar_hpcp(self._h, pcm_ptr, int(n), int(sample_rate), int(window_size), int(hop_size), wt,
                                        C.byref(p), hpcp_ptr, energy_ptr, entropy_ptr, 1))
+
+    def key_frames(self, chroma, params=None, skip=()):
+        """KeyEstimator.EstimateKey on every row of chroma (F x dim) (sonar_key_frames; params:
+        key_params(...), default NewKeyEstimator's) -> dict of key, mode, known, confidence, strength,
+        clarity, ambiguity, tonality (F), scores (F x 24), candidates (F x min(max_candidates, 24) codes
+        key * 2 + mode) and processed (F x hpcp_size); a name in skip is passed as NULL and comes back None."""
+        p = params if params is not None else key_params()
+        chroma = _key_rows(chroma)
+        F, dim = chroma.shape
+        o = _key_frame_arrays(F, p, skip)
+        self._check(self._L.sonar_key_frames(self._h, _ptr(chroma) if chroma.size else None, F, dim, C.byref(p),
+                                             *[_ptr(o[n]) for n in KEY_FRAME_FIELDS], 0))
+        return o
+
+    def key_frames_device(self, chroma_ptr, F, dim, params=None, **ptrs):
+        """key_frames on device memory (device_ptrs = 1): chroma (F x dim) and every output given by
+        keyword (the names of KEY_FRAME_FIELDS) are device addresses."""
+        p = params if params is not None else key_params()
+        self._check(self._L.sonar_key_frames(self._h, chroma_ptr, int(F), int(dim), C.byref(p),
+                                             *[ptrs.get(n) for n in KEY_FRAME_FIELDS], 1))
+
+    _KEY_SEQ_FIELDS = KEY_FRAME_FIELDS[:9] + ("processed", "stability", "modulations", "n_modulations")
+
+    def key_sequence(self, chroma, params=None, skip=()):
+        """KeyEstimator.EstimateKeySequence of chroma (F x dim) (sonar_key_sequence) -> dict of the average
+        row's key, mode, known, confidence, strength, clarity, ambiguity, tonality, scores (24), processed
+        (hpcp_size), and stability and modulations (the positions); a name in skip is passed as NULL."""
+        p = params if params is not None else key_params()
+        chroma = _key_rows(chroma)
+        F, dim = chroma.shape
+        o = _key_frame_arrays(1, p, skip)
+        del o["candidates"]
+        o["stability"] = None if "stability" in skip else np.zeros(1)
+        o["modulations"] = None if "modulations" in skip else np.zeros(max(F - 20, 0), np.int32)
+        o["n_modulations"] = None if "n_modulations" in skip else np.zeros(1, np.int64)
+        self._check(self._L.sonar_key_sequence(self._h, _ptr(chroma) if chroma.size else None, F, dim, C.byref(p),
+                                               *[_ptr(o[n]) for n in self._KEY_SEQ_FIELDS], 0))
+        r = {n: (None if v is None else v.reshape(v.shape[1:]) if n in ("scores", "processed") else
+                 v if n == "modulations" else v[0]) for n, v in o.items()}
+        if r["modulations"] is not None and r["n_modulations"] is not None:
+            r["modulations"] = r["modulations"][:int(r["n_modulations"])]
+        return r
+
+    def key_sequence_device(self, chroma_ptr, F, dim, params=None, **ptrs):
+        """key_sequence on device memory (device_ptrs = 1): chroma and every output given by keyword (key,
+        ..., scores, processed, stability, modulations, n_modulations; the single values too) are device
+        addresses; modulations holds max(F - 20, 0) int32, n_modulations one int64."""
+        p = params if params is not None else key_params()
+        self._check(self._L.sonar_key_sequence(self._h, chroma_ptr, int(F), int(dim), C.byref(p),
+                                               *[ptrs.get(n) for n in self._KEY_SEQ_FIELDS], 1))
+
+    _KEY_BATCH_FIELDS = KEY_FRAME_FIELDS + ("global_code", "global_confidence", "global_strength", "votes", "t_frame",
+                                            "t_from", "t_to", "t_confidence", "t_type", "n_transitions")
+
+    def key_batch(self, chroma, params=None, skip=()):
+        """KeyEstimationBatch on chroma (F x dim) (sonar_key_batch): ProcessBatch's per-frame outputs as
+        key_frames', GetGlobalKey's global_code (-1: no vote), global_confidence, global_strength and
+        votes (24, by code), and GetKeyProgression's records t_frame, t_from, t_to (codes), t_confidence,
+        t_type (an index of KEY_TRANSITIONS), cut to n_transitions; a name in skip is passed as NULL."""
+        p = params if params is not None else key_params()
+        chroma = _key_rows(chroma)
+        F, dim = chroma.shape
+        o = _key_frame_arrays(F, p, skip)
+        cap = max(F - 1, 0)
+        extra = {"global_code": ((1,), np.int32), "global_confidence": ((1,), np.float64),
+                 "global_strength": ((1,), np.float64), "votes": ((24,), np.float64), "t_frame": ((cap,), np.int32),
+                 "t_from": ((cap,), np.int32), "t_to": ((cap,), np.int32), "t_confidence": ((cap,), np.float64),
+                 "t_type": ((cap,), np.int32), "n_transitions": ((1,), np.int64)}
+        for n, (shape, dt) in extra.items():
+            o[n] = None if n in skip else np.zeros(shape, dt)
+        self._check(self._L.sonar_key_batch(self._h, _ptr(chroma) if chroma.size else None, F, dim, C.byref(p),
+                                            *[_ptr(o[n]) for n in self._KEY_BATCH_FIELDS], 0))
+        for n in ("global_code", "global_confidence", "global_strength", "n_transitions"):
+            if o[n] is not None:
+                o[n] = o[n][0]
+        if o["n_transitions"] is not None:
+            for n in ("t_frame", "t_from", "t_to", "t_confidence", "t_type"):
+                if o[n] is not None:
+                    o[n] = o[n][:int(o["n_transitions"])]
+        return o
+
+    def key_batch_device(self, chroma_ptr, F, dim, params=None, **ptrs):
+        """key_batch on device memory (device_ptrs = 1): chroma and every output given by keyword (the names
+        key_batch returns) are device addresses; the t_ arrays hold max(F - 1, 0) entries."""
+        p = params if params is not None else key_params()
+        self._check(self._L.sonar_key_batch(self._h, chroma_ptr, int(F), int(dim), C.byref(p),
+                                            *[ptrs.get(n) for n in self._KEY_BATCH_FIELDS], 1))
 
     def music_alignment_features(self, pcm, sample_rate, stft_window=1024, stft_hop=256, feature_window=1024,
                                  feature_hop=256):
