@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <mutex>
 
+#include "go_math.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -29,7 +30,6 @@
 namespace sonar {
 
 namespace {
-// math.Min (Go): NaN propagates, -Inf wins, -0 < +0
 // sqrt(x) for x in [2^-767, +Inf): LLVM's correctly rounded f64 sqrt sequence (v_rsq_f64 + two
 // Goldschmidt/Newton refinements) without its range scaling (an ldexp by 0 there) and its
 // 0 / Inf class fix-up (not taken there), so the same bits as sqrt() in 10 instructions instead
@@ -46,14 +46,6 @@ __device__ __forceinline__ double sqrt_normal(double x) {
   return __builtin_fma(d, h, g);
 }
 constexpr double DTW_SQRT_MIN = 0x1p-767;   // below: the full sqrt() (its scaled range)
-
-__device__ __forceinline__ double go_min(double x, double y) {
-  if (__builtin_isinf(x) && x < 0) return x;
-  if (__builtin_isinf(y) && y < 0) return y;
-  if (__builtin_isnan(x) || __builtin_isnan(y)) return __builtin_nan("");
-  if (x == 0 && x == y) return __builtin_signbit(x) ? x : y;
-  return x < y ? x : y;
-}
 }  // namespace
 
 // ---------------------------------------------------------------- NCC ----

@@ -1,7 +1,8 @@
 // chroma_sim_api.cpp -- sonar_chroma_frame_matrix / sonar_chroma_similarity / sonar_chroma_similarity_plan:
 // ChromaSequenceSimilarity.ComputeSimilarity (algorithms/chroma/chroma_similarity.go:86-538).  The host
 // side: Go's integer arithmetic (the sample step, the OTI column ranges, the DTW band rule), the choice
-// of the transposition from the device's ordered sums, the empty-input results and the scratch.  The
+// of the transposition from the device's ordered sums, the empty-input results and the scratch; the
+// sequences, the matrix and the path arrays are the caller's host or device arrays (staging.h).  The
 // kernels are chroma_sim_kernels.hip's.
 #include <cmath>
 #include <cstdint>
@@ -12,6 +13,7 @@
 
 #include "ctx.h"
 #include "kernels.h"
+#include "staging.h"
 
 namespace {
 using namespace sonar::detail;
@@ -67,17 +69,11 @@ struct Stages {
 };
 
 // device copies of the two sequences (their own when they are device pointers)
-int stage_inputs(sonar_ctx* c, bool dev, const double* q, int64_t nq, const double* r, int64_t nr, int dim,
-                 const double** dq, const double** dr) {
-  *dq = q; *dr = r;
-  if (dev) return SONAR_OK;
-  double* pq = (double*)dbuf(c, "csim.q", (size_t)nq * dim * 8);
-  double* pr = (double*)dbuf(c, "csim.r", (size_t)nr * dim * 8);
-  if (!pq || !pr) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (chroma sequences)");
-  HIP_TRY(c, hipMemcpyAsync(pq, q, (size_t)nq * dim * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(pr, r, (size_t)nr * dim * 8, hipMemcpyHostToDevice, c->stream));
-  *dq = pq; *dr = pr;
-  return SONAR_OK;
+int stage_inputs(Staging& o, const double* q, int64_t nq, const double* r, int64_t nr, int dim, const double** dq,
+                 const double** dr) {
+  *dq = o.in("q", q, (size_t)nq * dim);
+  *dr = o.in("r", r, (size_t)nr * dim);
+  return o.ready("device allocation failed (chroma sequences)");
 }
 
 int check_inputs(sonar_ctx* c, const double* q, int64_t nq, const double* r, int64_t nr, int32_t dim) {
@@ -136,14 +132,14 @@ int sonar_chroma_frame_matrix(sonar_ctx* c, const double* q, int64_t nq, const d
   if (!out) return fail(c, SONAR_ERR_INVALID, "chroma frame matrix: null output pointer");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const bool dev = is_dev(q);
+  Staging o{c, "csim.", is_dev(q)};
   const double *dq, *dr;
-  if (const int rc = stage_inputs(c, dev, q, nq, r, nr, dim, &dq, &dr)) return rc;
+  if (const int rc = stage_inputs(o, q, nq, r, nr, dim, &dq, &dr)) return rc;
   const int64_t rl = sonar::chroma_row_len(dim);
-  double* qp = (double*)dbuf(c, "csim.qp", (size_t)nq * rl * 8);
-  double* rp = (double*)dbuf(c, "csim.rp", (size_t)nr * rl * 8);
-  double* dout = dev ? out : (double*)dbuf(c, "csim.out", (size_t)nq * nr * 8);
-  if (!qp || !rp || !dout) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (chroma frame matrix)");
+  double* qp = o.tmp<double>("qp", (size_t)nq * rl);
+  double* rp = o.tmp<double>("rp", (size_t)nr * rl);
+  double* dout = o.out("out", out, (size_t)nq * nr);
+  if (const int rc = o.ready("device allocation failed (chroma frame matrix)")) return rc;
   Stages st{c, s};
   st.begin(0);
   hipEvent_t tend = timed_begin(c, s);
@@ -158,8 +154,7 @@ int sonar_chroma_frame_matrix(sonar_ctx* c, const double* q, int64_t nq, const d
   if (lrc != 0) return fail(c, SONAR_ERR_DEVICE, "chroma frame matrix launch failed");
   timed_end(c, s, tend);
   st.end(0);
-  if (!dev) HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)nq * nr * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  if (const int rc = o.finish()) return rc;
   st.finish();
   return SONAR_OK;
 }
@@ -200,9 +195,9 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
     return fail(c, SONAR_ERR_UNSUPPORTED, "chroma similarity: Smith-Waterman and DTW take at most 2^30 cells (nq * nr)");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const bool dev = is_dev(q);
+  Staging o{c, "csim.", is_dev(q)};
   const double *dq, *dr;
-  if (const int rc = stage_inputs(c, dev, q, nq, r, nr, dim, &dq, &dr)) return rc;
+  if (const int rc = stage_inputs(o, q, nq, r, nr, dim, &dq, &dr)) return rc;
   const int64_t rl = sonar::chroma_row_len(dim), cells = nq * nr, cap = nq + nr;
   const double total = (double)(nq * nr);            // float64(queryLen*refLen), float64(count)
   double* rp = (double*)dbuf(c, "csim.rp", (size_t)nr * rl * 8);
@@ -259,11 +254,7 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
     return SONAR_OK;
   };
   // the device matrix the caller gets: its own device pointer, or scratch copied back at the end
-  auto out_matrix = [&]() -> double* { return !matrix ? nullptr : dev ? matrix : (double*)dbuf(c, "csim.out", (size_t)cells * 8); };
-  auto copy_matrix = [&](const double* from) -> int {
-    if (matrix && !dev) HIP_TRY(c, hipMemcpyAsync(matrix, from, (size_t)cells * 8, hipMemcpyDeviceToHost, s));
-    return SONAR_OK;
-  };
+  auto out_matrix = [&](const char* name) { return o.out(name, matrix, (size_t)cells); };
 
   if (m == SONAR_CHROMA_SIM_OTI) {                   // :400-445; ignores TranspositionInvariant
     if (const int rc = ordered(1)) return rc;
@@ -276,16 +267,15 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
     }
     best = b; ov = mx;
     if (matrix) {
-      double* dout = out_matrix();
+      double* dout = out_matrix("out");
       if (!dout) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (similarity matrix)");
       sonar::ChromaMatArgs a{};
       a.qp = qp + (int64_t)b * nq * rl; a.mode = 1; a.banded = 1; a.radius = oti_radius; a.out = dout;
       st.begin(0);
       if (const int rc = launch_matrix(a)) return rc;
       st.end(0);
-      if (const int rc = copy_matrix(dout)) return rc;
     }
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if (const int rc = o.finish()) return rc;
     st.finish();
     return done();
   }
@@ -303,7 +293,7 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
     hipEvent_t tend = timed_begin(c, s);
     if (!ti)
       if (const int rc = prepare_shift0()) return rc;
-    double* dout = out_matrix();
+    double* dout = out_matrix("out");
     if (matrix && !dout) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (similarity matrix)");
     const bool want_sum = m == SONAR_CHROMA_SIM_DIRECT && !ti;
     const int64_t nblk = sonar::chroma_matrix_blocks(nq, nr);
@@ -322,8 +312,7 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
     st.end(0);
     unsigned long long h[3];
     HIP_TRY(c, hipMemcpyAsync(h, red, sizeof h, hipMemcpyDeviceToHost, s));
-    if (const int rc = copy_matrix(dout)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if (const int rc = o.finish()) return rc;
     st.finish();
     double sum, mx;
     std::memcpy(&sum, &h[0], 8);
@@ -337,7 +326,8 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   // Smith-Waterman (:197-271) and the file's DTW (:274-352): the frame matrix, then the recurrence in
   // place on it, then the walk back.  Neither applies a transposition.
   const bool dtw = m == SONAR_CHROMA_SIM_DTW;
-  double* M = (!dtw && matrix && dev) ? matrix : (double*)dbuf(c, "csim.M", (size_t)cells * 8);
+  // SW: SimilarityMatrix is scores[1:][1:] (:252-258), so the recurrence runs in the caller's matrix
+  double* M = (!dtw && matrix) ? out_matrix("M") : o.tmp<double>("M", (size_t)cells);
   int32_t* pq = (int32_t*)dbuf(c, "csim.pq", (size_t)cap * 4);
   int32_t* pr = (int32_t*)dbuf(c, "csim.pr", (size_t)cap * 4);
   double* ps = (double*)dbuf(c, "csim.ps", (size_t)cap * 8);
@@ -351,7 +341,7 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   }
   double* dsim = nullptr;
   if (dtw && matrix) {                               // SimilarityMatrix = exp(-cost) (:332-338)
-    dsim = out_matrix();
+    dsim = out_matrix("out");
     if (!dsim) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (similarity matrix)");
     if (sonar::launch_chroma_exp_neg(M, cells, dsim, s) != 0) return fail(c, SONAR_ERR_DEVICE, "chroma exp launch failed");
   }
@@ -394,14 +384,12 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   else HIP_TRY(c, hipMemcpyAsync(&best_score, dscal, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(&P, dscal + 2, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (P > 0) {                                       // written back to front: the path is the tail
-    if (path_q) HIP_TRY(c, hipMemcpyAsync(path_q, pq + cap - P, (size_t)P * 4, kind, s));
-    if (path_r) HIP_TRY(c, hipMemcpyAsync(path_r, pr + cap - P, (size_t)P * 4, kind, s));
-    if (path_score) HIP_TRY(c, hipMemcpyAsync(path_score, ps + cap - P, (size_t)P * 8, kind, s));
+    if (const int rc = o.give(path_q, pq + cap - P, (size_t)P * 4)) return rc;
+    if (const int rc = o.give(path_r, pr + cap - P, (size_t)P * 4)) return rc;
+    if (const int rc = o.give(path_score, ps + cap - P, (size_t)P * 8)) return rc;
   }
-  if (const int rc = copy_matrix(dtw ? dsim : M)) return rc;    // SW: SimilarityMatrix is scores[1:][1:] (:252-258)
-  HIP_TRY(c, hipStreamSynchronize(s));
+  if (const int rc = o.finish()) return rc;
   st.finish();
   // SW: maxScore / len(path) (:261); DTW: exp(-(acc[nq-1][nr-1] / len(path))) (:341-342)
   ov = dtw ? std::exp(-(acc_end / (double)P)) : best_score / (double)P;

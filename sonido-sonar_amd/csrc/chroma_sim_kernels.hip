@@ -14,6 +14,7 @@
 
 #include <cstdint>
 
+#include "go_math.h"
 #include "kernels.h"
 
 namespace sonar {
@@ -22,21 +23,6 @@ namespace {
 
 constexpr int T = CHROMA_DP_T;
 
-// math.Max / math.Min (Go): +Inf / -Inf win, then NaN propagates, +0 > -0
-__device__ __forceinline__ double go_max(double x, double y) {
-  if (__builtin_isinf(x) && x > 0) return x;
-  if (__builtin_isinf(y) && y > 0) return y;
-  if (__builtin_isnan(x) || __builtin_isnan(y)) return __builtin_nan("");
-  if (x == 0 && x == y) return __builtin_signbit(x) ? y : x;
-  return x > y ? x : y;
-}
-__device__ __forceinline__ double go_min(double x, double y) {
-  if (__builtin_isinf(x) && x < 0) return x;
-  if (__builtin_isinf(y) && y < 0) return y;
-  if (__builtin_isnan(x) || __builtin_isnan(y)) return __builtin_nan("");
-  if (x == 0 && x == y) return __builtin_signbit(x) ? x : y;
-  return x < y ? x : y;
-}
 __device__ __forceinline__ double lane_bcast(double v, int j) {
   const long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), j);

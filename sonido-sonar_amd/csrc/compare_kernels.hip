@@ -18,28 +18,13 @@
 
 #include <cmath>
 
+#include "go_math.h"
 #include "kernels.h"
 
 namespace sonar {
 namespace {
 
 constexpr int kBlock = 256;
-
-// ---- Go math helpers (NaN behaviour of math.Max / math.Min) ---------------------------
-__device__ __forceinline__ double go_max(double x, double y) {
-  if (isinf(x) && x > 0) return x;
-  if (isinf(y) && y > 0) return y;
-  if (isnan(x) || isnan(y)) return NAN;
-  if (x == 0 && x == y) return signbit(x) ? y : x;
-  return x > y ? x : y;
-}
-__device__ __forceinline__ double go_min(double x, double y) {
-  if (isinf(x) && x < 0) return x;
-  if (isinf(y) && y < 0) return y;
-  if (isnan(x) || isnan(y)) return NAN;
-  if (x == 0 && x == y) return signbit(x) ? x : y;
-  return x < y ? x : y;
-}
 
 // gonum floats.Norm(x, 2) = f64.L2NormUnitary: scaled sum of squares
 __device__ double l2norm(const double* x, int n) {

@@ -13,8 +13,10 @@
 #include <vector>
 
 #include "ctx.h"
+#include "go_math.h"
 #include "kernels.h"
 
+using sonar::go_max;
 using sonar::detail::dbuf;
 using sonar::detail::fail;
 
@@ -88,14 +90,6 @@ int from_metadata(const char* ct, const char* genre, const char* station, const 
   if (!c.empty()) return parse_content_type(c);
   if (!g.empty()) return infer_from_genre(g);
   return infer_from_station(station ? station : "", url ? url : "");
-}
-
-double go_max(double x, double y) {
-  if (std::isinf(x) && x > 0) return x;
-  if (std::isinf(y) && y > 0) return y;
-  if (std::isnan(x) || std::isnan(y)) return NAN;
-  if (x == 0 && x == y) return std::signbit(x) ? y : x;
-  return x > y ? x : y;
 }
 
 }  // namespace

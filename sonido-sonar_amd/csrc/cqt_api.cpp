@@ -1,8 +1,9 @@
 // cqt_api.cpp -- sonar_chroma_cqt_plan / sonar_chroma_cqt: ChromaCQT.ComputeChroma
 // (algorithms/chroma/chroma_cqt.go:69-92).  The host side of computeCQTKernel (:95-165): the bin
 // frequencies, kernel lengths, FFT size and the taps in the reference's order of operations; the
-// chroma class of every bin (:224-230, :245-252); the frame count (:169-172).  The kernels are
-// cqt_kernels.hip's.
+// chroma class of every bin (:224-230, :245-252); the frame count (:169-172).  Taps and classes are one
+// cached table per parameter set (ctx.h, cached_table); the PCM and the outputs are staged by
+// staging.h.  The kernels are cqt_kernels.hip's.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -12,10 +13,13 @@
 #include <vector>
 
 #include "ctx.h"
+#include "go_math.h"
 #include "kernels.h"
+#include "staging.h"
 
-using sonar::detail::dbuf;
+using sonar::go_log2;
 using sonar::detail::fail;
+using sonar::detail::Staging;
 using sonar::detail::timed_begin;
 using sonar::detail::timed_end;
 
@@ -23,15 +27,6 @@ namespace {
 
 constexpr int64_t kMaxBins = 65536;                 // bins (Go has no limit; the table would not fit long before)
 constexpr int64_t kMaxTableDoubles = int64_t(1) << 27;   // 1 GiB of padded taps
-
-// math.Log2 (Go's log10.go): Frexp, an exact answer for powers of two, else exp + Log(frac) * (1 / Ln2).
-// int(Log2(max / min) * bins) truncates, so the last bit decides the bin count at whole octaves.
-double go_log2(double x) {
-  int e = 0;
-  const double fr = std::frexp(x, &e);
-  if (fr == 0.5) return (double)(e - 1);
-  return (double)e + std::log(fr) * (1.0 / M_LN2);
-}
 
 struct CqtPlan {
   int64_t K = 0, N = 0, F = 0, sum_taps = 0;
@@ -92,7 +87,7 @@ int cqt_plan(int32_t sr, double minf, double maxf, int32_t bpo, double q, double
   return SONAR_OK;
 }
 
-// The device tables of one parameter set, cached in the context under the set's bits until sonar_trim:
+// The device table of one parameter set, cached in the context under the set's bits until sonar_trim:
 // the padded taps by bin group (kernels.h, CqtArgs), the groups' offsets and padded lengths, the classes.
 struct CqtTables {
   const double* tab;
@@ -108,7 +103,6 @@ int cqt_tables(sonar_ctx* c, const CqtPlan& p, int32_t sr, double q, double minf
   std::memcpy(&b[0], &minf, 8); std::memcpy(&b[1], &maxf, 8); std::memcpy(&b[2], &q, 8); std::memcpy(&b[3], &tuning, 8);
   std::snprintf(key, sizeof key, "cqt.%d.%d.%016llx.%016llx.%016llx.%016llx", sr, bpo, (unsigned long long)b[0],
                 (unsigned long long)b[1], (unsigned long long)b[2], (unsigned long long)b[3]);
-  const std::string base(key);
   const int ng = (int)((p.K + sonar::CQT_BK - 1) / sonar::CQT_BK);
   std::vector<int64_t> goff((size_t)ng);
   std::vector<int32_t> lpad((size_t)ng);
@@ -122,14 +116,15 @@ int cqt_tables(sonar_ctx* c, const CqtPlan& p, int32_t sr, double q, double minf
     total += (int64_t)sonar::CQT_BK * lpad[(size_t)g];
   }
   if (total > kMaxTableDoubles) return fail(c, SONAR_ERR_UNSUPPORTED, "chroma CQT: the tap table of this configuration exceeds 1 GiB");
-  const size_t meta_bytes = (size_t)ng * 8 + (size_t)ng * 4 + (size_t)p.K * 4;
-  auto it = c->bufs.find(base + ".tab");
-  auto im = c->bufs.find(base + ".meta");
-  if (it == c->bufs.end() || !it->second.ptr || im == c->bufs.end() || !im->second.ptr) {
-    std::vector<double> tab((size_t)total, 0.0);
+  // one image: the taps, then the groups' offsets and padded lengths and the bins' classes
+  const size_t tab_bytes = (size_t)total * 8, meta_bytes = (size_t)ng * 8 + (size_t)ng * 4 + (size_t)p.K * 4;
+  const unsigned char* img = nullptr;
+  const int rc = sonar::detail::cached_table(c, key, "chroma CQT tap table", [&](std::vector<unsigned char>& image, int64_t&) {
+    image.assign(tab_bytes + meta_bytes, 0);
+    double* tab = (double*)image.data();
     for (int64_t k = 0; k < p.K; ++k) {
       const int g = (int)(k / sonar::CQT_BK);
-      double* row = tab.data() + goff[(size_t)g] + (k % sonar::CQT_BK) * (int64_t)lpad[(size_t)g];
+      double* row = tab + goff[(size_t)g] + (k % sonar::CQT_BK) * (int64_t)lpad[(size_t)g];
       const double freq = p.freq[(size_t)k];
       const int32_t L = p.len[(size_t)k];
       const double bandwidth = freq / q;                                  // :120
@@ -144,28 +139,16 @@ int cqt_tables(sonar_ctx* c, const CqtPlan& p, int32_t sr, double q, double minf
         row[i] = std::hypot(window * cs, window * sn);                    // cmplx.Abs of the product :135, :309
       }
     }
-    std::vector<unsigned char> meta(meta_bytes);
-    std::memcpy(meta.data(), goff.data(), (size_t)ng * 8);
-    std::memcpy(meta.data() + (size_t)ng * 8, lpad.data(), (size_t)ng * 4);
-    std::memcpy(meta.data() + (size_t)ng * 12, p.cls.data(), (size_t)p.K * 4);
-    void* dt = dbuf(c, base + ".tab", (size_t)total * 8);
-    void* dm = dbuf(c, base + ".meta", meta_bytes);
-    bool ok = dt && dm;
-    ok = ok && hipMemcpyAsync(dt, tab.data(), (size_t)total * 8, hipMemcpyHostToDevice, c->stream) == hipSuccess;
-    ok = ok && hipMemcpyAsync(dm, meta.data(), meta_bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;             // the host vectors go out of scope
-    if (!ok) {
-      for (const char* sfx : {".tab", ".meta"}) {
-        auto e = c->bufs.find(base + sfx);
-        if (e != c->bufs.end()) { if (e->second.ptr) hipFree(e->second.ptr); c->bufs.erase(e); }
-      }
-      return fail(c, SONAR_ERR_NOMEM, "device allocation failed (chroma CQT tap table)");
-    }
-    it = c->bufs.find(base + ".tab");
-    im = c->bufs.find(base + ".meta");
-  }
-  const unsigned char* m = (const unsigned char*)im->second.ptr;
-  out->tab = (const double*)it->second.ptr;
+    unsigned char* meta = image.data() + tab_bytes;
+    std::memcpy(meta, goff.data(), (size_t)ng * 8);
+    std::memcpy(meta + (size_t)ng * 8, lpad.data(), (size_t)ng * 4);
+    std::memcpy(meta + (size_t)ng * 12, p.cls.data(), (size_t)p.K * 4);
+    return SONAR_OK;
+  }, &img);
+  // an upload that failed is reported like an allocation that failed, as before
+  if (rc != SONAR_OK) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (chroma CQT tap table)");
+  const unsigned char* m = img + tab_bytes;
+  out->tab = (const double*)img;
   out->goff = (const int64_t*)m;
   out->lpad = (const int32_t*)(m + (size_t)ng * 8);
   out->cls = (const int32_t*)(m + (size_t)ng * 12);
@@ -209,18 +192,15 @@ int sonar_chroma_cqt(sonar_ctx* c, const double* pcm, int64_t n, int64_t hop, in
   CqtTables T{};
   const int trc = cqt_tables(c, p, sample_rate, q_factor, min_freq, max_freq, bins_per_octave, tuning_freq, &T);
   if (trc != SONAR_OK) return trc;
-  const double* dx = pcm;
-  if (!device_ptrs) {
-    double* px = (double*)dbuf(c, "cqt.pcm", (size_t)n * 8);
-    if (!px) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(px, pcm, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    dx = px;
-  }
-  const size_t cqt_bytes = (size_t)p.F * (size_t)p.K * 8, chroma_bytes = (size_t)p.F * 12 * 8;
-  double* dq = (device_ptrs && cqt) ? cqt : (double*)dbuf(c, "cqt.out", cqt_bytes);
-  double* dc = device_ptrs ? chroma : (double*)dbuf(c, "cqt.chroma", chroma_bytes);
-  int32_t* flag = (int32_t*)dbuf(c, "cqt.flag", 16);
-  if (!dq || !dc || !flag) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+  Staging o{c, "cqt.", device_ptrs != 0};
+  const double* dx = o.in("pcm", pcm, (size_t)n);
+  // the kernel writes the constant-Q rows in every call: scratch when the caller does not take them
+  const size_t cqt_count = (size_t)p.F * (size_t)p.K;
+  double* dq = cqt ? o.out("out", cqt, cqt_count) : o.tmp<double>("out", cqt_count);
+  double* dc = o.out("chroma", chroma, (size_t)p.F * 12);
+  int32_t* flag = o.tmp<int32_t>("flag", 4);
+  const int src = o.ready("device allocation failed");
+  if (src != SONAR_OK) return src;
   // non-finite PCM is refused before any output is written
   int32_t hflag = 0;
   HIP_TRY(c, hipMemsetAsync(flag, 0, 4, s));
@@ -240,12 +220,7 @@ int sonar_chroma_cqt(sonar_ctx* c, const double* pcm, int64_t n, int64_t hop, in
   if (rc == -1) return fail(c, SONAR_ERR_UNSUPPORTED, "chroma CQT: more frames or bins than one launch takes");
   if (rc != 0) return fail(c, SONAR_ERR_DEVICE, "chroma CQT launch failed");
   timed_end(c, s, tend);
-  if (!device_ptrs) {
-    HIP_TRY(c, hipMemcpyAsync(chroma, dc, chroma_bytes, hipMemcpyDeviceToHost, s));
-    if (cqt) HIP_TRY(c, hipMemcpyAsync(cqt, dq, cqt_bytes, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(c, hipStreamSynchronize(s));
-  return SONAR_OK;
+  return o.finish();
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -17,6 +18,10 @@
 struct DevBuf {
   void* ptr = nullptr;
   size_t cap = 0;
+  // cached tables only (sonar::detail::cached_table): the upload completed, and what the builder
+  // wants kept with the entry (the HPCP table's entry count)
+  bool ready = false;
+  int64_t tag = 0;
 };
 
 struct FpTables {
@@ -83,9 +88,6 @@ struct sonar_ctx {
   // matrix, the ordered sums, the DP fill and the traceback, and the last call's times
   hipEvent_t csim_ev[8] = {};
   double csim_ms[4] = {0.0, 0.0, 0.0, 0.0};
-  // entries of the HPCP contribution tables whose device copies are in bufs under the same names
-  // (hpcp_api.cpp); an entry whose buffer sonar_trim has freed is rebuilt
-  std::map<std::string, int64_t> hpcp_tables;
 };
 
 // Named float64 arrays + scalars.  An array either owns its values (v) or points into a block the
@@ -130,6 +132,14 @@ namespace sonar {
 namespace detail {
 int fail(sonar_ctx* c, int code, const std::string& msg);
 void* dbuf(sonar_ctx* c, const std::string& name, size_t bytes);
+// The device table `name`, cached in c->bufs until sonar_trim.  When it is not there, build fills the
+// host image (and may set the tag kept with the entry); the image is uploaded on c->stream and the
+// stream synchronised, and only then does the entry become servable.  A failed build returns its own
+// code (it sets the error text), a failed allocation SONAR_ERR_NOMEM "device allocation failed
+// (<what>)", a failed upload SONAR_ERR_DEVICE; each of them leaves no entry behind.
+using TableBuilder = std::function<int(std::vector<unsigned char>& image, int64_t& tag)>;
+int cached_table(sonar_ctx* c, const std::string& name, const char* what, const TableBuilder& build,
+                 const unsigned char** table, int64_t* tag = nullptr);
 // frees every cached device / pinned host buffer of c (sonar_trim; the batch path's NOMEM retry)
 void trim_buffers(sonar_ctx* c);
 void* hbuf(sonar_ctx* c, const std::string& name, size_t bytes);

@@ -6,6 +6,8 @@
 #include <cmath>
 #include <limits>
 
+#include "go_math.h"
+
 namespace sonar {
 namespace host {
 
@@ -16,20 +18,6 @@ constexpr double kPi = 3.14159265358979323846;
 int64_t go_trunc(double x) {
   if (!(x >= -9.2233720368547758e18 && x < 9.2233720368547758e18)) return std::numeric_limits<int64_t>::min();
   return static_cast<int64_t>(x);
-}
-double go_min(double x, double y) {
-  if (std::isinf(x) && x < 0) return x;
-  if (std::isinf(y) && y < 0) return y;
-  if (std::isnan(x) || std::isnan(y)) return std::numeric_limits<double>::quiet_NaN();
-  if (x == 0 && x == y) return std::signbit(x) ? x : y;
-  return x < y ? x : y;
-}
-double go_max(double x, double y) {
-  if (std::isinf(x) && x > 0) return x;
-  if (std::isinf(y) && y > 0) return y;
-  if (std::isnan(x) || std::isnan(y)) return std::numeric_limits<double>::quiet_NaN();
-  if (x == 0 && x == y) return std::signbit(x) ? y : x;
-  return x > y ? x : y;
 }
 double bessel_i0(double x) {   // windowing.go:425-441
   double sum = 1.0, term = 1.0;

@@ -2,8 +2,9 @@
 // companions: SpectralPeaks.DetectPeaks (algorithms/harmonic/spectral_peaks.go:36-100) and
 // HPCP.ComputeFromSpectrum (algorithms/chroma/hpcp.go:205-221).  The host side: the argument checks,
 // the contribution table (frequencyToPitchClass :224-236, addPeakContribution :254-281,
-// computeWindowWeight :284-300, addHarmonicContributions :303-321, evaluated per FFT bin with libm),
-// its per-context cache, and sonar_hpcp's chunk loop over the float64 transform.  The kernel is
+// computeWindowWeight :284-300, addHarmonicContributions :303-321, evaluated per FFT bin with libm)
+// as one cached table per parameter set (ctx.h, cached_table), the staged arrays of each entry
+// (staging.h), and sonar_hpcp's chunk loop over the float64 transform.  The kernel is
 // hpcp_kernels.hip's.
 #include <algorithm>
 #include <cmath>
@@ -14,10 +15,13 @@
 #include <vector>
 
 #include "ctx.h"
+#include "go_math.h"
 #include "kernels.h"
+#include "staging.h"
 
-using sonar::detail::dbuf;
+using sonar::go_log2;
 using sonar::detail::fail;
+using sonar::detail::Staging;
 using sonar::detail::timed_begin;
 using sonar::detail::timed_end;
 
@@ -30,14 +34,6 @@ constexpr int64_t kChunkBytes = int64_t(64) << 20;   // sonar_hpcp's magnitude s
 // ComputeFromSpectrum's detector (:211-216)
 constexpr double kHpcpMinHeight = 0.00001, kHpcpMinDistanceHz = 20.0;
 constexpr int32_t kHpcpMaxPeaks = 60;
-
-// math.Log2 (Go's log10.go): Frexp, an exact answer for powers of two, else exp + Log(frac) * (1 / Ln2)
-double go_log2(double x) {
-  int e = 0;
-  const double fr = std::frexp(x, &e);
-  if (fr == 0.5) return (double)(e - 1);
-  return (double)e + std::log(fr) * (1.0 / M_LN2);
-}
 
 // max(int(min_distance_hz / freq_res), 1) (:41-43).  Out of int64's range (or NaN) amd64's conversion
 // gives the most negative value, so 1; a distance of K bins or more acts like K.
@@ -181,7 +177,6 @@ int device_table(sonar_ctx* c, int32_t sample_rate, int32_t window_size, int32_t
                     ? p.weight_type : 0,
                 p.band_preset != 0, std::max(p.max_harmonics, 0), (unsigned long long)b[0], (unsigned long long)b[1],
                 (unsigned long long)b[2], (unsigned long long)b[3], (unsigned long long)b[4], (unsigned long long)b[5]);
-  const std::string name(key);
   auto layout = [&](int64_t n, size_t off[4]) {
     off[0] = 0;
     off[1] = ((size_t)K + 2) / 2 * 8;                       // row_start: K + 1 int32, padded to 8 bytes
@@ -189,17 +184,16 @@ int device_table(sonar_ctx* c, int32_t sample_rate, int32_t window_size, int32_t
     off[3] = off[2] + (size_t)n * 8;                       // factor
     return off[3] + (size_t)n * 8;                         // weight
   };
-  auto ib = c->bufs.find(name);
-  auto in = c->hpcp_tables.find(name);
   size_t off[4];
-  if (ib == c->bufs.end() || !ib->second.ptr || in == c->hpcp_tables.end()) {
+  const unsigned char* base = nullptr;
+  int64_t entries = 0;                                      // kept with the cached entry: it lays the arrays out
+  const int trc = sonar::detail::cached_table(c, key, "HPCP contribution table", [&](std::vector<unsigned char>& img, int64_t& n) {
     HpcpTable t;
     std::string msg;
     const int rc = build_table(sample_rate, window_size, K, p, t, msg);
     if (rc != SONAR_OK) return fail(c, rc, msg);
-    const int64_t n = (int64_t)t.wbin.size();
-    const size_t bytes = layout(n, off);
-    std::vector<unsigned char> img(bytes, 0);
+    n = (int64_t)t.wbin.size();
+    img.assign(layout(n, off), 0);
     int32_t* rs = (int32_t*)img.data();
     for (int32_t i = 0; i <= K; ++i) rs[i] = (int32_t)t.row_start[(size_t)i];
     if (n > 0) {
@@ -207,27 +201,14 @@ int device_table(sonar_ctx* c, int32_t sample_rate, int32_t window_size, int32_t
       std::memcpy(img.data() + off[2], t.factor.data(), (size_t)n * 8);
       std::memcpy(img.data() + off[3], t.weight.data(), (size_t)n * 8);
     }
-    void* dt = dbuf(c, name, bytes);
-    if (!dt) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (HPCP contribution table)");
-    HIP_TRY(c, hipMemcpyAsync(dt, img.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));             // the image goes out of scope
-    c->hpcp_tables[name] = n;
-    ib = c->bufs.find(name);
-    in = c->hpcp_tables.find(name);
-  }
-  layout(in->second, off);
-  const unsigned char* base = (const unsigned char*)ib->second.ptr;
+    return (int)SONAR_OK;
+  }, &base, &entries);
+  if (trc != SONAR_OK) return trc;
+  layout(entries, off);
   out->row_start = (const int32_t*)base;
   out->wbin = (const int32_t*)(base + off[1]);
   out->factor = (const double*)(base + off[2]);
   out->weight = (const double*)(base + off[3]);
-  return SONAR_OK;
-}
-
-int zero_out(sonar_ctx* c, void* p, size_t bytes, bool dev) {
-  if (!p || bytes == 0) return SONAR_OK;
-  if (dev) HIP_TRY(c, hipMemsetAsync(p, 0, bytes, c->stream));
-  else std::memset(p, 0, bytes);
   return SONAR_OK;
 }
 
@@ -298,14 +279,9 @@ int sonar_spectral_peaks(sonar_ctx* c, const double* mag, int64_t F, int32_t K, 
   if (F < 0 || K < 0) return fail(c, SONAR_ERR_INVALID, "spectral peaks: negative row count or row length");
   if (F == 0) return SONAR_OK;
   if (!count) return fail(c, SONAR_ERR_INVALID, "spectral peaks: null count pointer");
-  const bool dev = device_ptrs != 0;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (K == 0) {                                             // :37-39
-    const int zrc = zero_out(c, count, (size_t)F * 4, dev);
-    if (zrc != SONAR_OK) return zrc;
-    if (dev) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SONAR_OK;
-  }
+  Staging o{c, "peaks.", device_ptrs != 0};
+  if (K == 0) return o.zero({{count, (size_t)F * 4}});      // :37-39
   if (max_peaks < 0)                                        // peaks[:maxPeaks] :95-97
     return fail(c, SONAR_ERR_PANIC, "runtime error: slice bounds out of range [:" + std::to_string(max_peaks) + "]");
   std::string msg;
@@ -316,42 +292,27 @@ int sonar_spectral_peaks(sonar_ctx* c, const double* mag, int64_t F, int32_t K, 
   if (P > 0 && (!bin || !magnitude)) return fail(c, SONAR_ERR_INVALID, "spectral peaks: null bin or magnitude pointer");
   hipStream_t s = c->stream;
   const size_t slots = (size_t)F * (size_t)P;
-  const double* dm = mag;
-  int32_t *dc = count, *db = bin;
-  double *dpm = magnitude, *dpf = frequency;
-  if (!dev) {
-    double* pm = (double*)dbuf(c, "peaks.mag", (size_t)F * (size_t)K * 8);
-    dc = (int32_t*)dbuf(c, "peaks.count", (size_t)F * 4);
-    db = (int32_t*)dbuf(c, "peaks.bin", slots * 4);
-    dpm = (double*)dbuf(c, "peaks.pmag", slots * 8);
-    dpf = frequency ? (double*)dbuf(c, "peaks.pfreq", slots * 8) : nullptr;
-    if (!pm || !dc || !db || !dpm || (frequency && !dpf)) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(pm, mag, (size_t)F * (size_t)K * 8, hipMemcpyHostToDevice, s));
-    dm = pm;
-  }
   sonar::HpcpArgs a{};
-  a.mag = dm; a.F = F; a.K = K;
+  a.mag = o.in("mag", mag, (size_t)F * (size_t)K);
+  a.F = F; a.K = K;
   a.freq_res = (double)sample_rate / (double)window_size;   // :41
   a.min_height = min_height;
   a.min_dist = min_distance_bins(min_distance_hz, a.freq_res, K);
   a.P = (int)P;
-  a.count = dc;
-  if (P > 0) { a.bin = db; a.pmag = dpm; a.pfreq = dpf; }
+  a.count = o.out("count", count, (size_t)F);
+  if (P > 0) {
+    a.bin = o.out("bin", bin, slots);
+    a.pmag = o.out("pmag", magnitude, slots);
+    a.pfreq = o.out("pfreq", frequency, slots);
+  }
+  const int src = o.ready("device allocation failed");
+  if (src != SONAR_OK) return src;
   hipEvent_t tend = timed_begin(c, s);
   const int rc = sonar::launch_hpcp(a, s);
   if (rc == -1) return fail(c, SONAR_ERR_UNSUPPORTED, "spectral peaks: a shape the kernel does not take");
   if (rc != 0) return fail(c, SONAR_ERR_DEVICE, "spectral peaks launch failed");
   timed_end(c, s, tend);
-  if (!dev) {
-    HIP_TRY(c, hipMemcpyAsync(count, dc, (size_t)F * 4, hipMemcpyDeviceToHost, s));
-    if (slots > 0) {
-      HIP_TRY(c, hipMemcpyAsync(bin, db, slots * 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipMemcpyAsync(magnitude, dpm, slots * 8, hipMemcpyDeviceToHost, s));
-      if (frequency) HIP_TRY(c, hipMemcpyAsync(frequency, dpf, slots * 8, hipMemcpyDeviceToHost, s));
-    }
-  }
-  HIP_TRY(c, hipStreamSynchronize(s));
-  return SONAR_OK;
+  return o.finish();
 }
 
 int sonar_hpcp_table(int32_t sample_rate, int32_t window_size, int32_t K, const sonar_hpcp_params* params,
@@ -385,44 +346,26 @@ int sonar_hpcp_from_spectrum(sonar_ctx* c, const double* mag, int64_t F, int32_t
   int rc = check_params(p, msg);
   if (rc == SONAR_OK) rc = check_rates(sample_rate, window_size, K, msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
-  const bool dev = device_ptrs != 0;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const size_t prof_bytes = (size_t)F * (size_t)p.size * 8;
+  Staging o{c, "hpcp.", device_ptrs != 0};
+  const size_t prof = (size_t)F * (size_t)p.size;
   if (p.size == 0 || K == 0) {                              // no bins, or no peaks: zeros all through
     if (p.size > 0 && !hpcp) return fail(c, SONAR_ERR_INVALID, "HPCP: null hpcp pointer");
-    for (auto z : {std::make_pair((void*)hpcp, prof_bytes), std::make_pair((void*)energy, (size_t)F * 8),
-                   std::make_pair((void*)entropy, (size_t)F * 8)}) {
-      const int zrc = zero_out(c, z.first, z.second, dev);
-      if (zrc != SONAR_OK) return zrc;
-    }
-    if (dev) HIP_TRY(c, hipStreamSynchronize(s));
-    return SONAR_OK;
+    return o.zero({{hpcp, prof * 8}, {energy, (size_t)F * 8}, {entropy, (size_t)F * 8}});
   }
   if (!mag || !hpcp) return fail(c, SONAR_ERR_INVALID, "HPCP: null magnitude or hpcp pointer");
   DevTable T{};
   rc = device_table(c, sample_rate, window_size, K, p, &T);
   if (rc != SONAR_OK) return rc;
-  const double* dm = mag;
-  double *dh = hpcp, *de = energy, *dn = entropy;
-  if (!dev) {
-    double* pm = (double*)dbuf(c, "hpcp.mag", (size_t)F * (size_t)K * 8);
-    dh = (double*)dbuf(c, "hpcp.out", prof_bytes);
-    de = energy ? (double*)dbuf(c, "hpcp.energy", (size_t)F * 8) : nullptr;
-    dn = entropy ? (double*)dbuf(c, "hpcp.entropy", (size_t)F * 8) : nullptr;
-    if (!pm || !dh || (energy && !de) || (entropy && !dn)) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(pm, mag, (size_t)F * (size_t)K * 8, hipMemcpyHostToDevice, s));
-    dm = pm;
-  }
+  const double* dm = o.in("mag", mag, (size_t)F * (size_t)K);
+  double* dh = o.out("out", hpcp, prof);
+  double* de = o.out("energy", energy, (size_t)F);
+  double* dn = o.out("entropy", entropy, (size_t)F);
+  rc = o.ready("device allocation failed");
+  if (rc != SONAR_OK) return rc;
   rc = profile_rows(c, dm, F, K, window_size, sample_rate, p, T, dh, de, dn);
   if (rc != SONAR_OK) return rc;
-  if (!dev) {
-    HIP_TRY(c, hipMemcpyAsync(hpcp, dh, prof_bytes, hipMemcpyDeviceToHost, s));
-    if (energy) HIP_TRY(c, hipMemcpyAsync(energy, de, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-    if (entropy) HIP_TRY(c, hipMemcpyAsync(entropy, dn, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(c, hipStreamSynchronize(s));
-  return SONAR_OK;
+  return o.finish();
 }
 
 int sonar_hpcp_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* frames, int64_t* chunk_frames,
@@ -456,33 +399,26 @@ int sonar_hpcp(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, 
   rc = check_params(p, msg);
   if (rc == SONAR_OK) rc = check_rates(sample_rate, window_size, K, msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
-  const bool dev = device_ptrs != 0;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
+  Staging o{c, "hpcp.", device_ptrs != 0};
   if (p.size > 0 && !hpcp) return fail(c, SONAR_ERR_INVALID, "HPCP: null hpcp pointer");
   DevTable T{};
   if (p.size > 0) {
     rc = device_table(c, sample_rate, window_size, K, p, &T);
     if (rc != SONAR_OK) return rc;
   }
-  const double* dx = pcm;
-  const size_t prof_bytes = (size_t)F * (size_t)p.size * 8;
-  double *dh = hpcp, *de = energy, *dn = entropy;
-  if (!dev) {
-    double* px = (double*)dbuf(c, "hpcp.pcm", (size_t)n * 8);
-    dh = (double*)dbuf(c, "hpcp.out", prof_bytes);
-    de = energy ? (double*)dbuf(c, "hpcp.energy", (size_t)F * 8) : nullptr;
-    dn = entropy ? (double*)dbuf(c, "hpcp.entropy", (size_t)F * 8) : nullptr;
-    if (!px || !dh || (energy && !de) || (entropy && !dn)) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(px, pcm, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    dx = px;
-  }
+  const double* dx = o.in("pcm", pcm, (size_t)n);
+  double* dh = o.out("out", hpcp, (size_t)F * (size_t)p.size);
+  double* de = o.out("energy", energy, (size_t)F);
+  double* dn = o.out("entropy", entropy, (size_t)F);
+  rc = o.ready("device allocation failed");
+  if (rc != SONAR_OK) return rc;
   // Chunks of chunk_frames rows through one bounded scratch: the transform of the chunk's samples
   // (frame f of the signal is frame f - f0 of the samples from f0 * hop on: every frame lies inside
   // the signal), then the profile of its rows; both are queued on the context's stream, so the
   // scratch is reused in stream order and the host waits once, at the end.
   const int64_t cf = chunk_frames_for(window_size);
-  double* scratch = (double*)dbuf(c, "hpcp.chunk", (size_t)std::min(cf, F) * (size_t)K * 8);
+  double* scratch = o.tmp<double>("chunk", (size_t)std::min(cf, F) * (size_t)K);
   if (!scratch) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (HPCP magnitude scratch)");
   for (int64_t f0 = 0; p.size > 0 && f0 < F; f0 += cf) {
     const int64_t nf = std::min(cf, F - f0);
@@ -495,19 +431,13 @@ int sonar_hpcp(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, 
                       dn ? dn + f0 : nullptr);
     if (rc != SONAR_OK) return rc;
   }
-  if (p.size == 0) {
-    for (auto z : {std::make_pair((void*)de, (size_t)F * 8), std::make_pair((void*)dn, (size_t)F * 8)}) {
-      const int zrc = zero_out(c, z.first, z.second, true);
+  if (p.size == 0) {                                        // the staged copies are device memory in both modes
+    for (double* z : {de, dn}) {
+      const int zrc = sonar::detail::zero_out(c, z, (size_t)F * 8, true);
       if (zrc != SONAR_OK) return zrc;
     }
   }
-  if (!dev) {
-    if (prof_bytes) HIP_TRY(c, hipMemcpyAsync(hpcp, dh, prof_bytes, hipMemcpyDeviceToHost, s));
-    if (energy) HIP_TRY(c, hipMemcpyAsync(energy, de, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-    if (entropy) HIP_TRY(c, hipMemcpyAsync(entropy, dn, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(c, hipStreamSynchronize(s));
-  return SONAR_OK;
+  return o.finish();
 }
 
 }  // extern "C"

@@ -3,8 +3,8 @@
 // (algorithms/tonal/key_estimation.go).  The host side: Go's panics and the argument checks, the
 // profile table (per (mode, key) the shifted profile's diffB and sumSqB of PearsonCorrelationFunc,
 // stats/distance.go:111-145, in Go's operation order) and resizeChromaVector's index table (:464-485),
-// cached in the context per (profile, dim, hpcp_size) until sonar_trim, and the launch sequences.  The
-// kernels are key_kernels.hip's.
+// one cached table per (profile, dim, hpcp_size) (ctx.h, cached_table), and the launch sequences over
+// the staged arrays (staging.h).  The kernels are key_kernels.hip's.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -13,10 +13,13 @@
 #include <vector>
 
 #include "ctx.h"
+#include "go_math.h"
 #include "kernels.h"
+#include "staging.h"
 
-using sonar::detail::dbuf;
+using sonar::go_log2;
 using sonar::detail::fail;
+using sonar::detail::Staging;
 using sonar::detail::timed_begin;
 using sonar::detail::timed_end;
 
@@ -39,14 +42,6 @@ const double kProfiles[7][2][12] = {
     {{5.0, 0.0, 0.0, 0.0, 3.0, 0.0, 0.0, 4.0, 0.0, 0.0, 0.0, 0.0},
      {5.0, 0.0, 0.0, 3.0, 0.0, 0.0, 0.0, 4.0, 0.0, 0.0, 0.0, 0.0}},
 };
-
-// math.Log2 (Go's log10.go)
-double go_log2(double x) {
-  int e = 0;
-  const double fr = std::frexp(x, &e);
-  if (fr == 0.5) return (double)(e - 1);
-  return (double)e + std::log(fr) * (1.0 / M_LN2);
-}
 
 int check_params(const sonar_key_params& p, int64_t F, int32_t dim, std::string& msg) {
   if (p.hpcp_size < 0) { msg = "runtime error: makeslice: len out of range"; return SONAR_ERR_PANIC; }   // :470
@@ -72,11 +67,10 @@ int device_tables(sonar_ctx* c, const sonar_key_params& p, int32_t dim, sonar::K
   const int hs = p.hpcp_size;
   char key[96];
   std::snprintf(key, sizeof key, "key.tab.%d.%d.%d", prof, dim, hs);
-  const std::string name(key);
   const size_t tab_bytes = (size_t)24 * sonar::KEY_TAB_ROW * 8;
-  auto it = c->bufs.find(name);
-  if (it == c->bufs.end() || !it->second.ptr) {
-    std::vector<unsigned char> img(tab_bytes + (size_t)hs * 4, 0);
+  const unsigned char* base = nullptr;
+  const int rc = sonar::detail::cached_table(c, key, "key profile table", [&](std::vector<unsigned char>& img, int64_t&) {
+    img.assign(tab_bytes + (size_t)hs * 4, 0);
     double* tab = (double*)img.data();
     for (int mode = 0; mode < 2; ++mode)
       for (int k = 0; k < 12; ++k) {
@@ -97,47 +91,11 @@ int device_tables(sonar_ctx* c, const sonar_key_params& p, int32_t dim, sonar::K
       const double src = (double)i * ratio;
       ridx[i] = (int64_t)src < dim ? (int32_t)src : -1;     // :474-477
     }
-    void* d = dbuf(c, name, img.size());
-    if (!d) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (key profile table)");
-    HIP_TRY(c, hipMemcpyAsync(d, img.data(), img.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));             // the image goes out of scope
-    it = c->bufs.find(name);
-  }
-  const unsigned char* base = (const unsigned char*)it->second.ptr;
+    return SONAR_OK;
+  }, &base);
+  if (rc != SONAR_OK) return rc;
   a->tab = (const double*)base;
   a->ridx = dim != hs ? (const int32_t*)(base + tab_bytes) : nullptr;
-  return SONAR_OK;
-}
-
-// Where an output lives during the call: the caller's device array, or a named scratch that is copied
-// back to the caller's host array at the end.
-struct Outs {
-  sonar_ctx* c;
-  bool dev;
-  bool nomem = false;
-  struct Back { void* host; const void* devp; size_t bytes; };
-  std::vector<Back> back;
-  template <typename T>
-  T* out(const char* name, T* user, size_t count) {
-    if (!user) return nullptr;
-    if (dev) return user;
-    T* d = (T*)dbuf(c, std::string("key.o.") + name, count * sizeof(T));
-    if (!d) { nomem = true; return nullptr; }
-    back.push_back({user, d, count * sizeof(T)});
-    return d;
-  }
-  template <typename T>
-  T* tmp(const char* name, size_t count) {
-    T* d = (T*)dbuf(c, std::string("key.t.") + name, count * sizeof(T));
-    if (!d) nomem = true;
-    return d;
-  }
-};
-
-int zero_out(sonar_ctx* c, void* p, size_t bytes, bool dev) {
-  if (!p || bytes == 0) return SONAR_OK;
-  if (dev) HIP_TRY(c, hipMemsetAsync(p, 0, bytes, c->stream));
-  else std::memset(p, 0, bytes);
   return SONAR_OK;
 }
 
@@ -159,7 +117,7 @@ void base_args(const sonar_key_params& p, int32_t dim, sonar::KeyArgs& a) {
   a.log2_24 = go_log2(24.0);
 }
 
-void frame_outs(Outs& o, const FrameOuts& u, size_t F, const sonar::KeyArgs& base, sonar::KeyArgs& a) {
+void frame_outs(Staging& o, const FrameOuts& u, size_t F, const sonar::KeyArgs& base, sonar::KeyArgs& a) {
   a.key = o.out("key", u.key, F);
   a.mode = o.out("mode", u.mode, F);
   a.known = o.out("known", u.known, F);
@@ -180,31 +138,26 @@ int launch_rows(sonar_ctx* c, const sonar::KeyArgs& a) {
   return SONAR_OK;
 }
 
-// the chromagram on the device and the zeroed non-finite flag
-int stage_input(sonar_ctx* c, Outs& o, const double* chroma, int64_t F, int32_t dim, const double** din,
-                int32_t** flag) {
-  *din = chroma;
-  const size_t bytes = (size_t)F * (size_t)dim * 8;
-  if (!o.dev && bytes) {
-    double* d = o.tmp<double>("in", (size_t)F * (size_t)dim);
-    if (!d) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(d, chroma, bytes, hipMemcpyHostToDevice, c->stream));
-    *din = d;
-  }
-  *flag = o.tmp<int32_t>("flag", 1);
-  if (!*flag) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-  HIP_TRY(c, hipMemsetAsync(*flag, 0, 4, c->stream));
+// the chromagram on the device and the non-finite flag
+void stage_input(Staging& o, const double* chroma, int64_t F, int32_t dim, sonar::KeyArgs& a) {
+  a.chroma = o.in("in", chroma, (size_t)F * (size_t)dim);
+  a.nonfinite = o.tmp<int32_t>("flag", 1);
+}
+
+// after the allocations: the one out-of-memory report, the input copy and the zeroed flag, all queued
+int begin(sonar_ctx* c, Staging& o, int32_t* flag) {
+  const int rc = o.ready("device allocation failed");
+  if (rc != SONAR_OK) return rc;
+  HIP_TRY(c, hipMemsetAsync(flag, 0, 4, c->stream));
   return SONAR_OK;
 }
 
 // copies the host-mode outputs back, waits, and reports a non-finite input
-int finish(sonar_ctx* c, Outs& o, const int32_t* flag) {
-  hipStream_t s = c->stream;
+int finish(sonar_ctx* c, Staging& o, const int32_t* flag) {
   int32_t bad = 0;
-  HIP_TRY(c, hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
-  for (const auto& b : o.back)
-    if (b.bytes) HIP_TRY(c, hipMemcpyAsync(b.host, b.devp, b.bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, c->stream));
+  const int rc = o.finish();
+  if (rc != SONAR_OK) return rc;
   if (bad)
     return fail(c, SONAR_ERR_UNSUPPORTED,
                 "key estimation: a non-finite chroma value is not reproduced (a NaN score leaves the order of "
@@ -261,17 +214,17 @@ int sonar_key_frames(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim,
   int rc = common_checks(c, chroma, F, dim, params);
   if (rc != SONAR_OK || F == 0) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
-  Outs o{c, device_ptrs != 0};
+  Staging o{c, "key.", device_ptrs != 0};
   sonar::KeyArgs a{};
   base_args(*params, dim, a);
   rc = device_tables(c, *params, dim, &a);
   if (rc != SONAR_OK) return rc;
-  rc = stage_input(c, o, chroma, F, dim, &a.chroma, &a.nonfinite);
-  if (rc != SONAR_OK) return rc;
+  stage_input(o, chroma, F, dim, a);
   a.F = F;
   frame_outs(o, {key, mode, known, confidence, strength, clarity, ambiguity, tonality, scores, candidates, processed},
              (size_t)F, a, a);
-  if (o.nomem) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+  rc = begin(c, o, a.nonfinite);
+  if (rc != SONAR_OK) return rc;
   hipEvent_t tend = timed_begin(c, c->stream);
   rc = launch_rows(c, a);
   if (rc != SONAR_OK) return rc;
@@ -286,30 +239,21 @@ int sonar_key_sequence(sonar_ctx* c, const double* chroma, int64_t F, int32_t di
   if (!c) return SONAR_ERR_INVALID;
   if (F < 0 || dim < 0 || !params)
     return fail(c, SONAR_ERR_INVALID, "key estimation: negative frame count or row length, or null params");
-  const bool dev = device_ptrs != 0;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
+  Staging o{c, "key.", device_ptrs != 0};
   if (F == 0) {                                             // :251-253: the zero result
     const size_t hs = params->hpcp_size > 0 ? (size_t)params->hpcp_size : 0;
-    const std::pair<void*, size_t> z[] = {
-        {key, 4}, {mode, 4}, {known, 4}, {confidence, 8}, {strength, 8}, {clarity, 8}, {ambiguity, 8}, {tonality, 8},
-        {scores, 24 * 8}, {processed, hs * 8}, {stability, 8}, {n_modulations, 8}};
-    for (const auto& e : z) {
-      const int zrc = zero_out(c, e.first, e.second, dev);
-      if (zrc != SONAR_OK) return zrc;
-    }
-    if (dev) HIP_TRY(c, hipStreamSynchronize(s));
-    return SONAR_OK;
+    return o.zero({{key, 4}, {mode, 4}, {known, 4}, {confidence, 8}, {strength, 8}, {clarity, 8}, {ambiguity, 8},
+                   {tonality, 8}, {scores, 24 * 8}, {processed, hs * 8}, {stability, 8}, {n_modulations, 8}});
   }
   int rc = common_checks(c, chroma, F, dim, params);
   if (rc != SONAR_OK) return rc;
-  Outs o{c, dev};
   sonar::KeyArgs base{};
   base_args(*params, dim, base);
   rc = device_tables(c, *params, dim, &base);
   if (rc != SONAR_OK) return rc;
-  rc = stage_input(c, o, chroma, F, dim, &base.chroma, &base.nonfinite);
-  if (rc != SONAR_OK) return rc;
+  stage_input(o, chroma, F, dim, base);
   const double* din = base.chroma;
   // the average row and its estimate
   double* avg = o.tmp<double>("avg", (size_t)dim);
@@ -327,7 +271,8 @@ int sonar_key_sequence(sonar_ctx* c, const double* chroma, int64_t F, int32_t di
   int64_t* dnmod = o.out("nmod", n_modulations, 1);
   int32_t* wcode = want_mod && nw ? o.tmp<int32_t>("wcode", (size_t)nw) : nullptr;
   double* wconf = want_mod && nw ? o.tmp<double>("wconf", (size_t)nw) : nullptr;
-  if (o.nomem) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+  rc = begin(c, o, base.nonfinite);
+  if (rc != SONAR_OK) return rc;
   hipEvent_t tend = timed_begin(c, s);
   if (sonar::launch_key_colsum(din, F, dim, avg, s) != 0) return fail(c, SONAR_ERR_DEVICE, "key average launch failed");
   rc = launch_rows(c, one);
@@ -368,30 +313,22 @@ int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, 
   if (!c) return SONAR_ERR_INVALID;
   int rc = common_checks(c, chroma, F, dim, params);
   if (rc != SONAR_OK) return rc;
-  const bool dev = device_ptrs != 0;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
+  Staging o{c, "key.", device_ptrs != 0};
   if (F == 0) {                                             // :924-926, :963-965
     const int32_t none = -1;
     if (global_code) {
-      if (dev) HIP_TRY(c, hipMemcpyAsync(global_code, &none, 4, hipMemcpyHostToDevice, s));
+      if (o.dev) HIP_TRY(c, hipMemcpyAsync(global_code, &none, 4, hipMemcpyHostToDevice, s));
       else *global_code = none;
     }
-    const std::pair<void*, size_t> z[] = {{global_confidence, 8}, {global_strength, 8}, {votes, 24 * 8}, {n_transitions, 8}};
-    for (const auto& e : z) {
-      const int zrc = zero_out(c, e.first, e.second, dev);
-      if (zrc != SONAR_OK) return zrc;
-    }
-    if (dev) HIP_TRY(c, hipStreamSynchronize(s));
-    return SONAR_OK;
+    return o.zero({{global_confidence, 8}, {global_strength, 8}, {votes, 24 * 8}, {n_transitions, 8}});
   }
-  Outs o{c, dev};
   sonar::KeyArgs a{};
   base_args(*params, dim, a);
   rc = device_tables(c, *params, dim, &a);
   if (rc != SONAR_OK) return rc;
-  rc = stage_input(c, o, chroma, F, dim, &a.chroma, &a.nonfinite);
-  if (rc != SONAR_OK) return rc;
+  stage_input(o, chroma, F, dim, a);
   a.F = F;
   frame_outs(o, {key, mode, known, confidence, strength, clarity, ambiguity, tonality, scores, candidates, processed},
              (size_t)F, a, a);
@@ -399,7 +336,7 @@ int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, 
   const bool want_trans = t_frame || t_from || t_to || t_confidence || t_type || n_transitions;
   if (want_global || want_trans) {
     a.code = o.tmp<int32_t>("code", (size_t)F);
-    if (!a.conf) a.conf = o.tmp<double>("conf", (size_t)F);
+    if (!a.conf) a.conf = o.tmp<double>("fconf", (size_t)F);
   }
   int32_t* dg = o.out("gcode", global_code, 1);
   double* dgc = o.out("gconf", global_confidence, 1);
@@ -413,7 +350,8 @@ int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, 
   k.tconf = o.out("tconf", t_confidence, cap);
   k.type = o.out("ttype", t_type, cap);
   k.count = o.out("ntrans", n_transitions, 1);
-  if (o.nomem) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+  rc = begin(c, o, a.nonfinite);
+  if (rc != SONAR_OK) return rc;
   hipEvent_t tend = timed_begin(c, s);
   rc = launch_rows(c, a);
   if (rc != SONAR_OK) return rc;

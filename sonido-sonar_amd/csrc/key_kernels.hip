@@ -17,19 +17,12 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "go_math.h"
 #include "kernels.h"
 
 namespace sonar {
 
 namespace {
-
-// math.Log2 (Go's log10.go): Frexp, an exact answer for powers of two, else exp + Log(frac) * (1 / Ln2)
-__device__ inline double go_log2(double x) {
-  int e = 0;
-  const double fr = frexp(x, &e);
-  if (fr == 0.5) return (double)(e - 1);
-  return (double)e + log(fr) * (1.0 / 0.693147180559945309417232121458176568);
-}
 
 // The row-to-result computation: p holds the resized row (hs values, a lane's own LDS) and leaves it
 // preprocessed; s receives the 24 scores [12 major | 12 minor].

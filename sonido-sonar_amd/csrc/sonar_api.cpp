@@ -48,6 +48,42 @@ void* dbuf(sonar_ctx* c, const std::string& name, size_t bytes) {
   return b.ptr;
 }
 
+int cached_table(sonar_ctx* c, const std::string& name, const char* what, const TableBuilder& build,
+                 const unsigned char** table, int64_t* tag) {
+  auto it = c->bufs.find(name);
+  if (it == c->bufs.end() || !it->second.ptr || !it->second.ready) {
+    auto drop = [&]() {                                      // an unfilled buffer is never served later
+      auto e = c->bufs.find(name);
+      if (e == c->bufs.end()) return;
+      if (e->second.ptr) hipFree(e->second.ptr);
+      c->bufs.erase(e);
+    };
+    drop();
+    std::vector<unsigned char> image;
+    int64_t t = 0;
+    const int rc = build(image, t);
+    if (rc != SONAR_OK) return rc;
+    void* d = dbuf(c, name, image.size());
+    if (!d) {
+      drop();
+      return fail(c, SONAR_ERR_NOMEM, std::string("device allocation failed (") + what + ")");
+    }
+    hipError_t e = image.empty() ? hipSuccess
+                                 : hipMemcpyAsync(d, image.data(), image.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the image goes out of scope
+    if (e != hipSuccess) {
+      drop();
+      return fail(c, SONAR_ERR_DEVICE, std::string(what) + " upload: " + hipGetErrorString(e));
+    }
+    it = c->bufs.find(name);
+    it->second.tag = t;
+    it->second.ready = true;                                 // the one place an entry becomes servable
+  }
+  *table = (const unsigned char*)it->second.ptr;
+  if (tag) *tag = it->second.tag;
+  return SONAR_OK;
+}
+
 void* hbuf(sonar_ctx* c, const std::string& name, size_t bytes) {
   if (bytes == 0) bytes = 16;
   DevBuf& b = c->hbufs[name];

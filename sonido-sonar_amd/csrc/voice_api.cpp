@@ -16,30 +16,14 @@
 #include <vector>
 
 #include "ctx.h"
+#include "go_math.h"
 #include "host_dsp.h"
 #include "kernels.h"
 
+using sonar::go_max;
+using sonar::go_min;
 using sonar::detail::dbuf;
 using sonar::detail::fail;
-
-namespace {
-
-double go_max(double x, double y) {            // math.Max (NaN-propagating, +0 > -0)
-  if (std::isinf(x) && x > 0) return x;
-  if (std::isinf(y) && y > 0) return y;
-  if (std::isnan(x) || std::isnan(y)) return NAN;
-  if (x == 0 && x == y) return std::signbit(x) ? y : x;
-  return x > y ? x : y;
-}
-double go_min(double x, double y) {
-  if (std::isinf(x) && x < 0) return x;
-  if (std::isinf(y) && y < 0) return y;
-  if (std::isnan(x) || std::isnan(y)) return NAN;
-  if (x == 0 && x == y) return std::signbit(x) ? x : y;
-  return x < y ? x : y;
-}
-
-}  // namespace
 
 namespace sonar {
 namespace detail {

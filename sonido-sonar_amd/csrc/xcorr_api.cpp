@@ -2,7 +2,8 @@
 // AutoCorrelation.Compute (algorithms/stats/correlation.go:131-200, 669-690) for every correlation
 // type, method and constructor.  The kernels are xcorr_kernels.hip's (Pearson per lag, subtractMean,
 // the FFT method) and align_kernels.hip's (z-score, NCC lag sums); the peak, p-value and quality
-// metrics are host::ncc_metrics, as in sonar_ncc.
+// metrics are host::ncc_metrics, as in sonar_ncc.  The signals and the scratch are staged by staging.h;
+// the FFT twiddles are a cached table (ctx.h, cached_table).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -12,9 +13,10 @@
 #include "ctx.h"
 #include "host_dsp.h"
 #include "kernels.h"
+#include "staging.h"
 
-using sonar::detail::dbuf;
 using sonar::detail::fail;
+using sonar::detail::Staging;
 using sonar::detail::timed_begin;
 using sonar::detail::timed_end;
 
@@ -29,27 +31,21 @@ int64_t next_pow2(int64_t n) {
 
 // The (cos, sin) pairs of -2 pi m / N, m < N / 2, on the device: the twiddles of fft's top level
 // (:748), which serve every level by stride (xcorr_kernels.hip).  libm on the host, as the checker and the oracle.
-// Built once per N and context; the table is a cached buffer, so sonar_trim releases it.
+// One cached table per N and context (ctx.h, cached_table); sonar_trim releases it.  Null on failure.
 const double2* xcorr_twiddles(sonar_ctx* c, int64_t N) {
-  const std::string name = "xcorr.tw." + std::to_string(N);
-  auto it = c->bufs.find(name);
-  if (it != c->bufs.end() && it->second.ptr) return (const double2*)it->second.ptr;
-  const int64_t half = N / 2;
-  void* d = dbuf(c, name, (size_t)std::max<int64_t>(half, 1) * sizeof(double2));
-  if (!d) { c->bufs.erase(name); return nullptr; }
-  std::vector<double2> h((size_t)half);
-  for (int64_t m = 0; m < half; ++m) {
-    // one sincos call, as the oracle's cos(th), sin(th) pair compiles to: glibc's sincos and its
-    // sin / cos differ in the last bit for a few angles
-    ::sincos(-2.0 * M_PI * (double)m / (double)N, &h[(size_t)m].y, &h[(size_t)m].x);
-  }
-  if (half > 0 && (hipMemcpyAsync(d, h.data(), (size_t)half * sizeof(double2), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                   hipStreamSynchronize(c->stream) != hipSuccess)) {
-    hipFree(d);
-    c->bufs.erase(name);
-    return nullptr;
-  }
-  return (const double2*)d;
+  const unsigned char* tw = nullptr;
+  const int rc = sonar::detail::cached_table(c, "xcorr.tw." + std::to_string(N), "correlation FFT", [&](std::vector<unsigned char>& img, int64_t&) {
+    const int64_t half = N / 2;
+    img.resize((size_t)half * sizeof(double2));
+    double2* h = (double2*)img.data();
+    for (int64_t m = 0; m < half; ++m) {
+      // one sincos call, as the oracle's cos(th), sin(th) pair compiles to: glibc's sincos and its
+      // sin / cos differ in the last bit for a few angles
+      ::sincos(-2.0 * M_PI * (double)m / (double)N, &h[m].y, &h[m].x);
+    }
+    return SONAR_OK;
+  }, &tw);
+  return rc == SONAR_OK ? (const double2*)tw : nullptr;
 }
 
 // Compute (:131-200).  same: signal2 is signal1 (AutoCorrelation.Compute :682-684)
@@ -73,28 +69,24 @@ int xcorr_run(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_
   const int64_t L = sonar::detail::ncc_max_lag(max_lag, na, nb), nl = 2 * L + 1;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const double *da = a, *db = b;
-  if (!device_ptrs) {
-    double* pa = (double*)dbuf(c, "xcorr.a", na * 8);
-    double* pb = same ? pa : (double*)dbuf(c, "xcorr.b", nb * 8);
-    if (!pa || !pb) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(pa, a, na * 8, hipMemcpyHostToDevice, s));
-    if (!same) HIP_TRY(c, hipMemcpyAsync(pb, b, nb * 8, hipMemcpyHostToDevice, s));
-    da = pa; db = pb;
-  }
-  double* xa = (double*)dbuf(c, "xcorr.xa", na * 8);
-  double* xb = (double*)dbuf(c, "xcorr.xb", nb * 8);
-  double* st = (double*)dbuf(c, "xcorr.stats", 128);              // [0..3] z-score, [8..11] subtractMean
-  double* dc = (device_ptrs && corr) ? corr : (double*)dbuf(c, "xcorr.corr", nl * 8);
-  if (!xa || !xb || !st || !dc) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
+  Staging o{c, "xcorr.", device_ptrs != 0};
+  const double* da = o.in("a", a, (size_t)na);
+  const double* db = same ? da : o.in("b", b, (size_t)nb);
+  double* xa = o.tmp<double>("xa", (size_t)na);
+  double* xb = o.tmp<double>("xb", (size_t)nb);
+  double* st = o.tmp<double>("stats", 16);                        // [0..3] z-score, [8..11] subtractMean
+  // the correlation also goes to the host for the metrics, so a host array is filled from that copy
+  double* dc = (o.dev && corr) ? corr : o.tmp<double>("corr", (size_t)nl);
+  const int src = o.ready("device allocation failed");
+  if (src != SONAR_OK) return src;
   const double2* tw = nullptr;
   double2 *A = nullptr, *B = nullptr, *C = nullptr;
   if (fft) {
     tw = xcorr_twiddles(c, N);
-    A = (double2*)dbuf(c, "xcorr.fa", (size_t)N * sizeof(double2));
-    B = same ? A : (double2*)dbuf(c, "xcorr.fb", (size_t)N * sizeof(double2));
-    C = (double2*)dbuf(c, "xcorr.fc", (size_t)N * sizeof(double2));
-    if (!tw || !A || !B || !C) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (correlation FFT)");
+    A = o.tmp<double2>("fa", (size_t)N);
+    B = same ? A : o.tmp<double2>("fb", (size_t)N);
+    C = o.tmp<double2>("fc", (size_t)N);
+    if (!tw || o.nomem) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (correlation FFT)");
   }
   hipEvent_t tend = timed_begin(c, s);
   int rc = sonar::launch_ncc_zscore(da, na, db, nb, xa, xb, st, s);   // normalizeInputs is true in every constructor
@@ -115,8 +107,9 @@ int xcorr_run(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_
   timed_end(c, s, tend);
   std::vector<double> hc((size_t)nl);
   HIP_TRY(c, hipMemcpyAsync(hc.data(), dc, nl * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  if (corr && !device_ptrs) std::memcpy(corr, hc.data(), nl * 8);
+  const int frc = o.finish();
+  if (frc != SONAR_OK) return frc;
+  if (corr && !o.dev) std::memcpy(corr, hc.data(), nl * 8);
   if (metrics) {
     sonar::detail::ncc_metrics_host(hc.data(), L, na, nb, metrics);   // [0..9], as sonar_ncc
     metrics[10] = (double)method;
