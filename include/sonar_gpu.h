@@ -41,6 +41,11 @@
  *   sonar_key_sequence         <- KeyEstimator.EstimateKeySequence (key_estimation.go:250-270)
  *   sonar_key_batch            <- KeyEstimationBatch.ProcessBatch / GetGlobalKey / GetKeyProgression (:896-1005)
  *   sonar_key_transition       <- AnalyzeKeyTransition (:843-894)
+ *   sonar_chord_frames         <- ChordDetector.DetectChord from templateMatching on, per chroma row through a
+ *                                 fresh detector (algorithms/tonal/chord_detection.go:428-502)
+ *   sonar_chord_sequence       <- the same with one detector fed the rows in order (:783-806, :919-926)
+ *   sonar_chord_detect         <- ChordDetector.DetectChord per frame of PCM (:408-503, :506-531)
+ *   sonar_chord_progression    <- ChordProgressionAnalyzer.AnalyzeProgression (:1128-1173)
  *   sonar_ncc                  <- CrossCorrelation.Compute, NormalizedCrossCorrelation /
  *                                 TimeDomain (algorithms/stats/correlation.go:131)
  *   sonar_xcorr_params         <- CrossCorrelation.Compute for every type, method and constructor
@@ -648,6 +653,131 @@ int sonar_key_batch(sonar_ctx* ctx, const double* chroma /* F x dim */, int64_t 
  * min(distance, 12 - distance); *strength = 1 / (1 + fifths_distance).  Any output may be NULL. */
 int sonar_key_transition(int32_t from_key, int32_t from_mode, int32_t to_key, int32_t to_mode, int32_t* type,
                          int32_t* semitone_distance, int32_t* fifths_distance, double* strength);
+
+/* ---- chord detection over a chromagram (float64) ----------------------------
+ * ChordDetector (algorithms/tonal/chord_detection.go) on F rows of dim chroma values, for example the
+ * profile sonar_hpcp leaves on the device.  Nothing on the path calls a transcendental function.
+ *
+ * DetectChord (:408-503) of one row, from templateMatching (:586-641) on:
+ *   normalize_templates: the row is divided by sqrt(sum x^2) only when sum x^2 >= 1e-10
+ *   (common/normalization.go:113-134).  The 120 template scores are calculateTemplateScore (:721-733) of
+ *   the ten templates (Major 0, Minor 1, Diminished 2, Augmented 3, Sus2 4, Sus4 5, Maj7 6, Min7 7, Dom7 8,
+ *   PowerChord 23) rotated to the twelve roots, times the template's weight; a candidate's slot is
+ *   t * 12 + root with t the template's position in that order (the reference iterates a map there; this
+ *   is the order fixed here), and template_scores is indexed by slot.  Every score is 0
+ *   when dim is not 12 (F54).  With use_bass_detection and a bass confidence > 0.3 a candidate whose
+ *   chord tones hold the bass note gains bass_weight * bass_confidence (:735-750); a slot is a candidate
+ *   when its score >= min_chord_strength; with use_inversions and a bass confidence > 0.3,
+ *   detectInversion (:752-781: 1.5 at the bass tone) replaces strength and inversion when it scores
+ *   higher.  confidence = min(strength, 1).  The methods harmonic_analysis, cqt_based and statistical
+ *   match with the bass forced to (0, 0.0); every other value of method matches with the bass (F58).
+ *   applyTemporalSmoothing (:783-806, sonar_chord_sequence only): a candidate that is in chordHistory
+ *   has its confidence times 1.1, clipped to 1.  chordHistory aliases the candidate slice that is then
+ *   sorted in place: after a frame it is that frame's candidate set, minus its first-ranked candidate
+ *   when the history was not empty before the frame and the frame has more than temporal_window
+ *   candidates (F52); a frame without candidates empties it (F55).
+ *   The candidates are sorted by confidence, descending; sort.Slice leaves the order of equal
+ *   confidences open, here they stay in slot order (F50); the first max_candidates are kept.  root,
+ *   quality (Go's ChordQuality code), inversion, confidence and strength are the first kept candidate's;
+ *   clarity = c0 - c1 (c0 with one kept), ambiguity = 1 - clarity, consonance the template's, tension =
+ *   calculateHarmonicTension (:1012-1035) of the raw row, stability = max(0, 1 - variance) of
+ *   confidenceHistory (the first confidences of the last <= temporal_window earlier frames that kept a
+ *   candidate), or the confidence when that history is empty (always in sonar_chord_frames).
+ *   extensions (detect_extensions; :840-894) is a mask of 1 << interval over the intervals 2, 5, 9, 10, 11;
+ *   role (use_functional_analysis; :896-917) is 0 "", 1 tonic, 2 subdominant, 3 dominant, 4 leading_tone,
+ *   5 other.  A row that keeps no candidate is Go's zero result: every per-frame output 0 but n_found (F55).
+ * Errors, tested in Go's order and only when F > 0: dim not 12, 24 or 36 -> SONAR_ERR_INVALID "failed to
+ * extract chroma features: unsupported chroma size: N" (:416-419); max_candidates < 0 -> SONAR_ERR_PANIC
+ * "runtime error: slice bounds out of range [:-1]" (the value; :458-460, even for rows without
+ * candidates); a bass note outside 0..11 -> SONAR_ERR_INVALID; in a sequence, temporal_window < 0 at a
+ * frame without candidates after one with -> SONAR_ERR_PANIC "runtime error: slice bounds out of range
+ * [1:0]" (:802).  Not reproduced (SONAR_ERR_UNSUPPORTED, the message says which): a non-finite chroma
+ * value, bass confidence or parameter; temporal_window above 64; F above 2^31 - 1.
+ * F == 0 -> SONAR_OK, nothing is read or written.
+ * With device_ptrs = 1 the inputs and every output are device addresses; the call returns after the
+ * stream has drained either way.  Every output may be NULL and then costs nothing. */
+#define SONAR_CHORD_TEMPLATE_MATCHING 0
+#define SONAR_CHORD_HARMONIC_ANALYSIS 1
+#define SONAR_CHORD_CQT_BASED 2
+#define SONAR_CHORD_STATISTICAL 3
+#define SONAR_CHORD_ML_BASED 4
+#define SONAR_CHORD_HYBRID 5
+#define SONAR_CHORD_SLOTS 120
+/* The fields of ChordDetectionParams (:136-175) the reference reads (DESIGN.md F51 lists the others);
+ * ChromaSize is the row length dim. */
+typedef struct sonar_chord_params {
+  int32_t method;                  /* Method */
+  int32_t normalize_templates;     /* NormalizeTemplates */
+  int32_t use_inversions;          /* UseInversions */
+  int32_t max_candidates;          /* MaxCandidates */
+  int32_t use_bass_detection;      /* UseBassDetection */
+  int32_t detect_extensions;       /* DetectExtensions */
+  int32_t max_extension;           /* MaxExtension */
+  int32_t use_temporal_smoothing;  /* UseTemporalSmoothing */
+  int32_t temporal_window;         /* TemporalWindow */
+  int32_t use_functional_analysis; /* UseFunctionalAnalysis */
+  double min_chord_strength;       /* MinChordStrength */
+  double bass_weight;              /* BassWeight */
+} sonar_chord_params;
+/* NewChordDetector's values (:217-244): template matching, normalized, inversions, 5 candidates, bass
+ * detection, extensions up to 13, smoothing over 5, no functional analysis, 0.2, 0.3. */
+void sonar_chord_params_default(sonar_chord_params* p);
+/* The outputs of the chord entries: F entries each, template_scores F x 120, the candidate arrays
+ * F x max_candidates (slots, -1 and zeros beyond the kept ones). */
+typedef struct sonar_chord_out {
+  int32_t* root;
+  int32_t* quality;
+  int32_t* inversion;
+  int32_t* n_found;           /* candidates before the cut */
+  double* confidence;
+  double* strength;
+  double* clarity;
+  double* ambiguity;
+  double* consonance;
+  double* tension;
+  double* stability;
+  int32_t* extensions;
+  int32_t* role;
+  double* template_scores;
+  int32_t* candidates;
+  int32_t* cand_inversion;
+  double* cand_confidence;
+  double* cand_strength;
+} sonar_chord_out;
+/* Every row through a fresh detector: no boost, stability = confidence.  bass_note / bass_confidence: F
+ * entries each or NULL, what detectBassNote returned per row (NULL: 0 and 0.0). */
+int sonar_chord_frames(sonar_ctx* ctx, const double* chroma /* F x dim */, int64_t F, int32_t dim,
+                       const int32_t* bass_note, const double* bass_confidence, const sonar_chord_params* params,
+                       const sonar_chord_out* out, int32_t device_ptrs);
+/* One detector fed the rows in order: the smoothing chain and the stability history apply. */
+int sonar_chord_sequence(sonar_ctx* ctx, const double* chroma /* F x dim */, int64_t F, int32_t dim,
+                         const int32_t* bass_note, const double* bass_confidence, const sonar_chord_params* params,
+                         const sonar_chord_out* out, int32_t device_ptrs);
+/* DetectChord on every frame of frame_len samples at hop: (n - frame_len) / hop + 1 frames (*frames when
+ * not NULL; n < frame_len -> SONAR_ERR_TOO_SHORT).  extractChromaFeatures (:506-531) takes the first W =
+ * min(2048, frame_len) samples of the frame, unwindowed (F56), their full-length magnitude spectrum
+ * (mirror half included, F37) and ComputeFromSpectrum with NewHPCP's defaults; then one detector is fed
+ * the profiles in order as in sonar_chord_sequence.  hpcp (frames x 12 or NULL) receives the profiles.
+ * W must be a power-of-two window size of the fused STFT path, else SONAR_ERR_UNSUPPORTED.  DetectPitch
+ * rejects every frame whose length is not 1024, so the bass is (0, 0.0) there (F53) and the bass arrays
+ * are not read; at frame_len 1024 with use_bass_detection the caller supplies both bass arrays or the
+ * call is SONAR_ERR_UNSUPPORTED (the pitch detector's stateful post-processing is not reproduced).
+ * method cqt_based is SONAR_ERR_UNSUPPORTED here, and so are rows of 24 or 36 bins: the entry computes
+ * the 12-bin profile.  frames is a host address in both pointer modes. */
+int sonar_chord_detect(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t frame_len,
+                       int32_t hop, const int32_t* bass_note, const double* bass_confidence,
+                       const sonar_chord_params* params, const sonar_chord_out* out, double* hpcp, int64_t* frames,
+                       int32_t device_ptrs);
+/* AnalyzeProgression (:1128-1173) over the per-frame results of F chords.  *num_chords = F;
+ * *insufficient_data = 1 below two chords and nothing else is written (decided on the host: ctx may be
+ * NULL then, with host pointers).  Else *average_confidence = (the sum of confidence in frame order) / F
+ * and *most_common_quality = the most frequent quality code (the reference iterates a map; here the
+ * lowest code among equal counts).  root and inversion only name the chords of the reference's
+ * transition strings and may be NULL.  A quality outside 0..31 or a non-finite confidence ->
+ * SONAR_ERR_UNSUPPORTED. */
+int sonar_chord_progression(sonar_ctx* ctx, const int32_t* root, const int32_t* quality, const int32_t* inversion,
+                            const double* confidence, int64_t F, int64_t* num_chords, int32_t* insufficient_data,
+                            double* average_confidence, int32_t* most_common_quality, int32_t device_ptrs);
 
 /* ---- path B: normalized cross-correlation (float64) --------------------
  * corr has 2L+1 entries, L = max(0, min(max_lag, na-1, nb-1)); metrics[10] =

@@ -605,4 +605,50 @@ struct KeyCompactArgs {
 };
 int launch_key_compact(const KeyCompactArgs& a, hipStream_t s);
 
+// ChordDetector over a chromagram (chord_kernels.hip; algorithms/tonal/chord_detection.go).
+constexpr int CHORD_SLOTS = 120;          // candidates t * 12 + root, t the template's position in quality order
+constexpr int CHORD_ROWS = 63;            // rows a block reports; its lane 0 holds the row before them
+constexpr int CHORD_TILE_FRAMES = 1024;   // records per round of the chain
+constexpr int CHORD_MAX_WINDOW = 64;      // temporal_window the stability pass takes
+constexpr int CHORD_HIST_EMPTY = -2;      // chordHistory before a frame: empty,
+constexpr int CHORD_HIST_FULL = -1;       // the previous frame's whole candidate set, or (>= 0) that set minus a slot
+constexpr int CHORD_FLAG_NONFINITE = 1, CHORD_FLAG_BASS_NOTE = 2, CHORD_FLAG_SLICE_PANIC = 4, CHORD_FLAG_QUALITY = 8;
+// DetectChord per row.  record == 1: only rec is written (the chain's input); else the outputs, with the
+// history state of hstate (null: every row meets a fresh detector).
+struct ChordArgs {
+  const double* chroma;          // rows of dim values, dim in {12, 24, 36}
+  int64_t F;
+  int dim;
+  const int32_t* bass_note;      // [F] or null (0)
+  const double* bass_conf;       // [F] or null (0.0)
+  int match_bass;                // the bass pair reaches templateMatching
+  int normalize, use_inversions, detect_ext, max_ext, functional, smoothing;
+  int32_t max_cand;              // >= 0
+  double min_strength, bass_weight;
+  int record;
+  int32_t* rec;                  // [F x 4] n, topN, top0, top1
+  const int32_t* hstate;         // [F] CHORD_HIST_* before the frame, or null
+  const int32_t* kidx;           // [F + 1] frames before f that kept a candidate; read with kconf
+  double* kconf;                 // the kept frames' first confidences, compacted; or null
+  int32_t* flags;                // CHORD_FLAG_* are or-ed in
+  int32_t *root, *quality, *inversion, *n_found, *ext, *role;          // each [F] or null
+  double *conf, *strength, *clarity, *ambiguity, *consonance, *tension, *stability;
+  double* scores;                // [F x 120] or null
+  int32_t *cand, *cand_inv;      // [F x max_cand] or null
+  double *cand_conf, *cand_strength;
+};
+int launch_chord_rows(const ChordArgs& a, hipStream_t s);   // -1: a shape the kernel does not take
+// the recurrence over the records: hstate [F], kidx [F + 1]; sets CHORD_FLAG_SLICE_PANIC where Go's history[1:] panics
+int launch_chord_chain(const int32_t* rec, int64_t F, int smoothing, int window, int keeps, int32_t* hstate,
+                       int32_t* kidx, int32_t* flags, hipStream_t s);
+// stability[f] = max(0, 1 - variance) of the last min(window, kidx[f]) entries of kconf before kidx[f], where
+// frame f kept a candidate and that history is not empty; other entries keep what the row pass wrote
+int launch_chord_stability(const int32_t* kidx, const double* kconf, int64_t F, int window, double* stability,
+                           hipStream_t s);
+// AnalyzeProgression: the ordered sum of conf / F and the most frequent quality (the lowest code among equals)
+int launch_chord_progression(const int32_t* quality, const double* conf, int64_t F, double* avg, int32_t* most,
+                             int32_t* flags, hipStream_t s);
+// mag rows of W / 2 + 1 bins -> rows of W bins, full[W - k] = full[k]
+int launch_chord_mirror(const double* half, int64_t F, int W, double* full, hipStream_t s);
+
 }  // namespace sonar

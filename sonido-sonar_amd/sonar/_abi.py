@@ -89,6 +89,41 @@ KEY_FRAME_FIELDS = ("key", "mode", "known", "confidence", "strength", "clarity",
                     "candidates", "processed")
 
 
+class ChordParams(C.Structure):
+    """sonar_chord_params: the fields of ChordDetectionParams the reference reads (chord_detection.go:136-175)."""
+    _fields_ = [(n, C.c_int32) for n in ("method", "normalize_templates", "use_inversions", "max_candidates",
+                                         "use_bass_detection", "detect_extensions", "max_extension",
+                                         "use_temporal_smoothing", "temporal_window", "use_functional_analysis")] + \
+               [("min_chord_strength", C.c_double), ("bass_weight", C.c_double)]
+
+
+# the per-frame outputs of the chord entries, in the order of sonar_chord_out
+CHORD_FIELDS = ("root", "quality", "inversion", "n_found", "confidence", "strength", "clarity", "ambiguity",
+                "consonance", "tension", "stability", "extensions", "role", "template_scores", "candidates",
+                "cand_inversion", "cand_confidence", "cand_strength")
+_CHORD_INT_FIELDS = ("root", "quality", "inversion", "n_found", "extensions", "role", "candidates", "cand_inversion")
+
+
+class ChordOut(C.Structure):
+    """sonar_chord_out: one pointer per name of CHORD_FIELDS."""
+    _fields_ = [(n, C.c_void_p) for n in CHORD_FIELDS]
+
+
+# ChordDetectionMethod (SONAR_CHORD_*), ChordQuality's names (GetChordQualityName), the templates' quality
+# codes by slot // 12, analyzeFunctionalRole's strings by role code and the inversion suffixes of getChordName
+CHORD_METHODS = {"template_matching": 0, "harmonic_analysis": 1, "cqt_based": 2, "statistical": 3, "ml_based": 4,
+                 "hybrid": 5}
+CHORD_QUALITY_NAMES = ["major", "minor", "diminished", "augmented", "sus2", "sus4", "major7", "minor7", "dominant7",
+                       "minor-major7", "augmented7", "diminished7", "half-diminished7", "add9", "major9", "minor9",
+                       "dominant9", "major11", "minor11", "dominant11", "major13", "minor13", "dominant13", "power",
+                       "unknown"]
+CHORD_SLOT_QUALITIES = [0, 1, 2, 3, 4, 5, 6, 7, 8, 23]
+CHORD_ROLES = ["", "tonic", "subdominant", "dominant", "leading_tone", "other"]
+CHORD_INVERSIONS = ["", "/1st", "/2nd", "/3rd", "/4th"]
+CHORD_EXTENSION_ORDER = [10, 11, 2, 5, 9]
+CHORD_SLOTS = 120
+
+
 class FpOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ["mfcc", "magnitude", "centroid", "rolloff", "bandwidth", "flatness",
                                           "crest", "slope", "flux", "low_ratio", "high_ratio", "zcr", "energy",
@@ -280,6 +315,14 @@ def lib():
     L.sonar_key_sequence.argtypes = _key + [_vp] * 13 + [C.c_int32]
     L.sonar_key_batch.argtypes = _key + [_vp] * 21 + [C.c_int32]
     L.sonar_key_transition.argtypes = [C.c_int32] * 4 + [_i32p, _i32p, _i32p, _d]
+    L.sonar_chord_params_default.argtypes = [C.POINTER(ChordParams)]
+    L.sonar_chord_params_default.restype = None
+    _chord = [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, C.POINTER(ChordParams), C.POINTER(ChordOut), C.c_int32]
+    L.sonar_chord_frames.argtypes = _chord
+    L.sonar_chord_sequence.argtypes = _chord
+    L.sonar_chord_detect.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp,
+                                     C.POINTER(ChordParams), C.POINTER(ChordOut), _vp, _i64p, C.c_int32]
+    L.sonar_chord_progression.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32]
     L.sonar_ncc.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, _vp, C.c_int32]
@@ -546,6 +589,57 @@ def _key_frame_arrays(F, p, skip=()):
 def _key_rows(chroma):
     chroma = _f64(chroma)
     return chroma[None, :] if chroma.ndim == 1 else chroma
+
+
+def chord_params(**kw):
+    """sonar_chord_params with NewChordDetector's defaults (sonar_chord_params_default), fields overridden by
+    keyword; method takes a name of CHORD_METHODS or the enum value."""
+    p = ChordParams()
+    lib().sonar_chord_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "method" and isinstance(v, str):
+            v = CHORD_METHODS[v]
+        setattr(p, k, v)
+    return p
+
+
+def chord_quality_name(quality):
+    """GetChordQualityName of a ChordQuality code."""
+    return CHORD_QUALITY_NAMES[quality] if 0 <= quality < len(CHORD_QUALITY_NAMES) else "unknown"
+
+
+def chord_name(root, quality, inversion=0):
+    """getChordName: the root's name, the template's name unless it is "major" ("unknown" for a quality
+    without a template), and the inversion's suffix."""
+    name = KEY_NAMES[root % 12]
+    qn = CHORD_QUALITY_NAMES[quality] if quality in CHORD_SLOT_QUALITIES else "unknown"
+    if qn != "major":
+        name += qn
+    if 0 < inversion < len(CHORD_INVERSIONS):
+        name += CHORD_INVERSIONS[inversion]
+    return name
+
+
+def chord_extensions(mask):
+    """The raw intervals of an extensions mask, in the order of the reference's map literal."""
+    return [i for i in CHORD_EXTENSION_ORDER if mask >> i & 1]
+
+
+def _chord_arrays(F, p, skip=()):
+    """numpy outputs of the chord entries (None for the names in skip) and the sonar_chord_out over them."""
+    mc = max(p.max_candidates, 0)
+    o = {}
+    for n in CHORD_FIELDS:
+        shape = (F, CHORD_SLOTS) if n == "template_scores" else (F, mc) if n.startswith("cand") else (F,)
+        o[n] = None if n in skip else np.zeros(shape, np.int32 if n in _CHORD_INT_FIELDS else np.float64)
+    out = ChordOut(*[o[n].ctypes.data if o[n] is not None and o[n].size else None for n in CHORD_FIELDS])
+    return o, out
+
+
+def _chord_bass(bass_note, bass_confidence):
+    bn = None if bass_note is None else np.ascontiguousarray(bass_note, dtype=np.int32)
+    bc = None if bass_confidence is None else _f64(bass_confidence)
+    return bn, bc
 
 
 def spectral_peaks_width(K, max_peaks):
@@ -1106,6 +1200,83 @@ class Context:
         p = params if params is not None else key_params()
         self._check(self._L.sonar_key_batch(self._h, chroma_ptr, int(F), int(dim), C.byref(p),
                                             *[ptrs.get(n) for n in self._KEY_BATCH_FIELDS], 1))
+
+    def _chord_rows(self, fn, chroma, params, bass_note, bass_confidence, skip):
+        p = params if params is not None else chord_params()
+        chroma = _key_rows(chroma)
+        F, dim = chroma.shape
+        bn, bc = _chord_bass(bass_note, bass_confidence)
+        o, out = _chord_arrays(F, p, skip)
+        self._check(fn(self._h, _ptr(chroma) if chroma.size else None, F, dim, _ptr(bn), _ptr(bc), C.byref(p),
+                       C.byref(out), 0))
+        return o
+
+    def chord_frames(self, chroma, params=None, bass_note=None, bass_confidence=None, skip=()):
+        """ChordDetector.DetectChord from templateMatching on, every row of chroma (F x dim) through a fresh
+        detector (sonar_chord_frames; params: chord_params(...), default NewChordDetector's; bass_note /
+        bass_confidence: what detectBassNote returned per row, default 0 and 0.0) -> dict of the names of
+        CHORD_FIELDS: F entries each, template_scores F x 120, the candidate arrays F x max_candidates
+        (slots t * 12 + root, -1 beyond the kept ones); a name in skip is passed as NULL and comes back None."""
+        return self._chord_rows(self._L.sonar_chord_frames, chroma, params, bass_note, bass_confidence, skip)
+
+    def chord_sequence(self, chroma, params=None, bass_note=None, bass_confidence=None, skip=()):
+        """chord_frames with one detector fed the rows in order (sonar_chord_sequence): the temporal
+        smoothing and the stability history apply."""
+        return self._chord_rows(self._L.sonar_chord_sequence, chroma, params, bass_note, bass_confidence, skip)
+
+    def chord_rows_device(self, chroma_ptr, F, dim, params=None, sequence=True, bass_note_ptr=None,
+                          bass_confidence_ptr=None, **ptrs):
+        """chord_sequence (or chord_frames with sequence=False) on device memory (device_ptrs = 1): chroma,
+        the bass arrays and every output given by keyword (the names of CHORD_FIELDS) are device addresses."""
+        p = params if params is not None else chord_params()
+        out = ChordOut(*[ptrs.get(n) for n in CHORD_FIELDS])
+        fn = self._L.sonar_chord_sequence if sequence else self._L.sonar_chord_frames
+        self._check(fn(self._h, chroma_ptr, int(F), int(dim), bass_note_ptr, bass_confidence_ptr, C.byref(p),
+                       C.byref(out), 1))
+
+    def chord_detect(self, pcm, sample_rate, frame_len, hop, params=None, bass_note=None, bass_confidence=None,
+                     skip=()):
+        """ChordDetector.DetectChord on every frame of frame_len samples at hop, one detector in order
+        (sonar_chord_detect) -> chord_sequence's dict plus hpcp (frames x 12), the profiles the detector saw."""
+        p = params if params is not None else chord_params()
+        pcm = _f64(pcm)
+        n = len(pcm)
+        F = (n - frame_len) // hop + 1 if frame_len > 0 and hop > 0 and n >= frame_len else 0
+        bn, bc = _chord_bass(bass_note, bass_confidence)
+        o, out = _chord_arrays(F, p, skip)
+        o["hpcp"] = None if "hpcp" in skip else np.zeros((F, 12))
+        frames = C.c_int64()
+        self._check(self._L.sonar_chord_detect(self._h, _ptr(pcm) if n else None, n, int(sample_rate), int(frame_len),
+                                               int(hop), _ptr(bn), _ptr(bc), C.byref(p), C.byref(out),
+                                               _ptr(o["hpcp"]) if F else None, C.byref(frames), 0))
+        assert frames.value == F
+        return o
+
+    def chord_progression(self, quality, confidence, root=None, inversion=None):
+        """ChordProgressionAnalyzer.AnalyzeProgression over per-frame results (sonar_chord_progression) ->
+        dict of num_chords and insufficient_data, and with two chords or more average_confidence,
+        most_common_quality (the code) and most_common_quality_name."""
+        q = np.ascontiguousarray(quality, dtype=np.int32)
+        cf = _f64(confidence)
+        r = None if root is None else np.ascontiguousarray(root, dtype=np.int32)
+        iv = None if inversion is None else np.ascontiguousarray(inversion, dtype=np.int32)
+        num, ins, avg, most = C.c_int64(), C.c_int32(), C.c_double(), C.c_int32()
+        self._check(self._L.sonar_chord_progression(self._h, _ptr(r), _ptr(q) if q.size else None, _ptr(iv),
+                                                    _ptr(cf) if cf.size else None, len(q), C.byref(num), C.byref(ins),
+                                                    C.byref(avg), C.byref(most), 0))
+        o = {"num_chords": num.value, "insufficient_data": ins.value}
+        if not ins.value:
+            o.update(average_confidence=avg.value, most_common_quality=most.value,
+                     most_common_quality_name=chord_quality_name(most.value))
+        return o
+
+    def chord_progression_device(self, quality_ptr, confidence_ptr, F, num_chords_ptr=None,
+                                 insufficient_data_ptr=None, average_confidence_ptr=None,
+                                 most_common_quality_ptr=None):
+        """chord_progression on device memory (device_ptrs = 1): every array and single value is a device address."""
+        self._check(self._L.sonar_chord_progression(self._h, None, quality_ptr, None, confidence_ptr, int(F),
+                                                    num_chords_ptr, insufficient_data_ptr, average_confidence_ptr,
+                                                    most_common_quality_ptr, 1))
 
     def music_alignment_features(self, pcm, sample_rate, stft_window=1024, stft_hop=256, feature_window=1024,
                                  feature_hop=256):
