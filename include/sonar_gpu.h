@@ -36,6 +36,13 @@
  *   sonar_hpcp_table           <- frequencyToPitchClass, addPeakContribution, computeWindowWeight and
  *                                 addHarmonicContributions per FFT bin (hpcp.go:224-321)
  *   sonar_hpcp_plan            <- the frame count and the chunks sonar_hpcp works in
+ *   sonar_hps_from_spectrum    <- HarmonicProduct.ComputeHPS / ComputeHPSWithInterpolation, findF0Peak,
+ *                                 ComputeHarmonicStrength and ComputeHarmonicity per spectrum row
+ *                                 (algorithms/harmonic/harmonic_product.go:32-273)
+ *   sonar_hps                  <- HarmonicProduct.EstimateF0WithConfidence per frame of PCM (:61-91, :276-298)
+ *   sonar_hps_bins             <- findF0Peak's scan range (:128-139)
+ *   sonar_hps_optimal_harmonics <- HarmonicProduct.GetOptimalNumHarmonics (:301-314)
+ *   sonar_hps_plan             <- the frame count and the chunks sonar_hps works in
  *   sonar_key_frames           <- KeyEstimator.EstimateKey / EstimateKeyFromHPCP per chroma row,
  *                                 KeyEstimationBatch.ProcessBatch (algorithms/tonal/key_estimation.go:196-247, 911)
  *   sonar_key_sequence         <- KeyEstimator.EstimateKeySequence (key_estimation.go:250-270)
@@ -545,6 +552,71 @@ int sonar_hpcp_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* f
 int sonar_hpcp(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t window_size,
                int32_t hop_size, int32_t window_type, const sonar_hpcp_params* params, double* hpcp,
                double* energy /* frames or NULL */, double* entropy /* frames or NULL */, int32_t device_ptrs);
+
+/* ---- harmonic product spectrum (float64) -----------------------------------
+ * HarmonicProduct (algorithms/harmonic/harmonic_product.go) of NewHarmonicProduct(sample_rate,
+ * num_harmonics, min_f0, max_f0) on each of F rows of K magnitudes; window_size is the reference's
+ * signalLength and, as in sonar_hpcp_from_spectrum, K is the row length whatever window_size is.
+ *   ComputeHPS (:32-58): p[i] = row[i] * row[i]; hps = p; for h = 2 .. num_harmonics in order, with
+ *   L = K / h: nothing when L == 0 (h > K: downsampleSpectrum returns an empty slice),
+ *   else hps[i] *= (i < L ? p[i * h] : 0.0) for every i < K.  The multiplication by 0.0 happens, so an
+ *   Inf or NaN there gives NaN (F63).  One rounding per product, left to right; subnormal products
+ *   survive.  num_harmonics <= 1 leaves the power spectrum.
+ *   ComputeHPSWithInterpolation (:163-191), interpolated != 0: hps[i] *= interpolateSpectrum(p,
+ *   float64(i) / float64(h)) for every bin and every h, h > K included; interpolateSpectrum (:194-209)
+ *   is 0.0 at index >= float64(K - 1), else p[l] + frac * (p[l+1] - p[l]), unfused.
+ *   findF0Peak (:127-160): sonar_hps_bins' range, a strict > against 0.0 in ascending bin order: the
+ *   lowest bin among equal maxima, never a NaN, bin 0 when nothing in the range is above 0 or the
+ *   range is empty (the local-maximum check after the loop changes nothing, F65).
+ *   f0 = float64(bin) * (float64(sample_rate) / float64(window_size)), 0 for bin 0 (:84-90).
+ *   ComputeHarmonicStrength (:224-247) at that f0 and window_size: for h = 1 .. num_harmonics,
+ *   harmonicBin = (f0 * float64(h)) / freqResolution as written (bin * h only up to rounding, F66),
+ *   0 at harmonicBin >= float64(K), else interpolateSpectrum on the magnitudes.
+ *   ComputeHarmonicity (:250-273), the confidence of EstimateF0WithConfidence (:276-298): the sum of
+ *   strength^2 in harmonic order over the sum of row[i] * row[i] in bin order, 0 when that is 0 or
+ *   num_harmonics is 0.
+ * Outputs: f0_bin[F] and f0[F] are required; confidence[F], strengths[F x max(num_harmonics, 0)] and
+ * hps[F x K] (the spectrum the peak search ran on) may be NULL.  Rows with f0 == 0 get confidence 0
+ * and zero strengths.  F == 0 or K == 0 -> SONAR_OK, zeros where there is anything to write.
+ * Not reproduced (SONAR_ERR_UNSUPPORTED, the message says which): sample_rate or window_size <= 0;
+ * min_f0 or max_f0 non-finite or negative, or one whose quotient by the frequency resolution does not
+ * fit an int32 (Go's conversion is implementation-defined there); K > 8192; num_harmonics > 64;
+ * num_harmonics < 0 when confidence or strengths is asked for (Go's make panics, on rows with f0 > 0
+ * only).  Non-finite magnitudes are no error: they follow IEEE arithmetic as in Go. */
+int sonar_hps_from_spectrum(sonar_ctx* ctx, const double* mag /* F x K */, int64_t F, int32_t K,
+                            int32_t window_size, int32_t sample_rate, int32_t num_harmonics,
+                            double min_f0, double max_f0, int32_t interpolated,
+                            int32_t* f0_bin /* F */, double* f0 /* F */, double* confidence /* F or NULL */,
+                            double* strengths /* F x max(num_harmonics,0) or NULL */,
+                            double* hps /* F x K or NULL */, int32_t device_ptrs);
+/* findF0Peak's scan range for rows of K bins, host only (no context, no GPU): min_bin = int(min_f0 /
+ * freqResolution) raised to 1, max_bin = int(max_f0 / freqResolution) lowered to K - 1, both
+ * conversions truncating (:128-139).  min_bin > max_bin is an empty range (K == 0: max_bin -1).
+ * K < 0 -> SONAR_ERR_INVALID; the range errors of sonar_hps_from_spectrum (no message). */
+int sonar_hps_bins(int32_t sample_rate, int32_t window_size, int32_t K, double min_f0, double max_f0,
+                   int32_t* min_bin, int32_t* max_bin);
+/* GetOptimalNumHarmonics (:301-314), host only: m = int((float64(sample_rate) / 2) / min_f0); 5 when
+ * m > 7, m - 1 when m > 3, else 2.  SONAR_ERR_UNSUPPORTED: sample_rate <= 0, min_f0 non-finite or
+ * negative, or a quotient that does not fit an int32 (min_f0 == 0). */
+int sonar_hps_optimal_harmonics(int32_t sample_rate, double min_f0, int32_t* num_harmonics);
+/* The frames of sonar_hps on n samples and how it splits them, host only: sonar_hpcp_plan's values
+ * and errors, and SONAR_ERR_UNSUPPORTED for window_size < 2. */
+int sonar_hps_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* frames,
+                   int64_t* chunk_frames, int64_t* n_chunks);
+/* EstimateF0WithConfidence (:276-298) on every frame of window_size samples at hop_size, (n -
+ * window_size) / hop_size + 1 of them: applyWindow (:212-221), 0.5 (1 - cos(2 pi i / (N - 1))), symmetric
+ * and not energy-normalised, the float64 transform's magnitudes with K = window_size / 2 + 1, then
+ * sonar_hps_from_spectrum's row estimate with signalLength = window_size.  The rows go through a
+ * bounded device scratch, chunk_frames at a time (sonar_hps_plan), as in sonar_hpcp.  magnitude
+ * (frames x K or NULL) receives the rows; frames (host memory in both modes, or NULL) the frame count.
+ * The window sizes and errors are sonar_hpcp's (the fused transform at 128-2048, the DFT path for
+ * other sizes up to 8192); window_size < 2 -> SONAR_ERR_UNSUPPORTED (the window divides by N - 1);
+ * then sonar_hps_from_spectrum's. */
+int sonar_hps(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t window_size,
+              int32_t hop_size, int32_t num_harmonics, double min_f0, double max_f0, int32_t interpolated,
+              int32_t* f0_bin, double* f0, double* confidence /* or NULL */, double* strengths /* or NULL */,
+              double* magnitude /* frames x K or NULL */, int64_t* frames /* host, or NULL */,
+              int32_t device_ptrs);
 
 /* ---- key estimation over a chromagram (float64) ----------------------------
  * KeyEstimator (algorithms/tonal/key_estimation.go) on F rows of dim chroma values, for example the

@@ -204,10 +204,18 @@ void timed_end(sonar_ctx* c, hipStream_t s, hipEvent_t end);
 void ingest_release(sonar_ctx* c);
 // sonar_fingerprint with the PCM already on the device and host outputs (sonar_api.cpp)
 // [f_lo, f_hi): only those frames of the whole signal's STFT (device outputs, per-frame kernel)
+// raw_window: the window table is not energy-normalised (HarmonicProduct.applyWindow, sonar_hps); a
+// table of its own under its own cache key, the kernels are the same
 int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cfg* cfg, sonar_fp_out* out,
-                     bool pcm_dev, int64_t f_lo = 0, int64_t f_hi = -1);
+                     bool pcm_dev, int64_t f_lo = 0, int64_t f_hi = -1, bool raw_window = false);
 // sonar_fingerprint's argument checks in its order: SONAR_OK and the frame count, or the code and text
 int fp_check(const sonar_fp_cfg* cfg, int64_t n, bool have_pcm, int64_t* F, std::string* msg);
+// The entries that run rows of |X| through a bounded scratch (sonar_hpcp, sonar_hps; hpcp_api.cpp):
+// the transform's configuration (SONAR_FP_MAGNITUDE only, float64 all through, device pointers) and
+// the rows per chunk, about 64 MiB of them
+void magnitude_fp_cfg(int32_t sample_rate, int32_t window_size, int32_t hop_size, int32_t window_type,
+                      sonar_fp_cfg* cfg);
+int64_t magnitude_chunk_frames(int32_t window_size);
 // VoiceQualityAnalyzer.AnalyzeVoiceQuality on device-resident float64 samples (voice_api.cpp)
 int voice_quality(sonar_ctx* c, const double* dsig, int64_t n, int32_t sr, sonar_voice_quality_result* out);
 }  // namespace detail

@@ -233,7 +233,11 @@ int profile_rows(sonar_ctx* c, const double* dmag, int64_t F, int32_t K, int32_t
   return SONAR_OK;
 }
 
-void hpcp_fp_cfg(int32_t sample_rate, int32_t window_size, int32_t hop_size, int32_t window_type, sonar_fp_cfg* cfg) {
+}  // namespace
+
+namespace sonar {
+namespace detail {
+void magnitude_fp_cfg(int32_t sample_rate, int32_t window_size, int32_t hop_size, int32_t window_type, sonar_fp_cfg* cfg) {
   sonar_fp_cfg_default(cfg);
   cfg->window_size = window_size;
   cfg->hop_size = hop_size;
@@ -246,12 +250,15 @@ void hpcp_fp_cfg(int32_t sample_rate, int32_t window_size, int32_t hop_size, int
   cfg->device_ptrs = 1;
 }
 
-int64_t chunk_frames_for(int32_t window_size) {
+int64_t magnitude_chunk_frames(int32_t window_size) {
   const int64_t K = window_size / 2 + 1;
   return std::max<int64_t>(kChunkBytes / (K * 8), 1);
 }
+}  // namespace detail
+}  // namespace sonar
 
-}  // namespace
+using sonar::detail::magnitude_chunk_frames;
+using sonar::detail::magnitude_fp_cfg;
 
 extern "C" {
 
@@ -371,12 +378,12 @@ int sonar_hpcp_from_spectrum(sonar_ctx* c, const double* mag, int64_t F, int32_t
 int sonar_hpcp_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* frames, int64_t* chunk_frames,
                     int64_t* n_chunks) {
   sonar_fp_cfg cfg;
-  hpcp_fp_cfg(44100, window_size, hop_size, SONAR_WIN_HANN, &cfg);
+  magnitude_fp_cfg(44100, window_size, hop_size, SONAR_WIN_HANN, &cfg);
   int64_t F = 0;
   std::string msg;
   const int rc = sonar::detail::fp_check(&cfg, n, true, &F, &msg);
   if (rc != SONAR_OK) return rc;
-  const int64_t cf = chunk_frames_for(window_size);
+  const int64_t cf = magnitude_chunk_frames(window_size);
   if (frames) *frames = F;
   if (chunk_frames) *chunk_frames = cf;
   if (n_chunks) *n_chunks = (F + cf - 1) / cf;
@@ -389,7 +396,7 @@ int sonar_hpcp(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, 
   if (!c) return SONAR_ERR_INVALID;
   if (!params) return fail(c, SONAR_ERR_INVALID, "HPCP: null params");
   sonar_fp_cfg cfg;
-  hpcp_fp_cfg(sample_rate, window_size, hop_size, window_type, &cfg);
+  magnitude_fp_cfg(sample_rate, window_size, hop_size, window_type, &cfg);
   int64_t F = 0;
   std::string msg;
   int rc = sonar::detail::fp_check(&cfg, n, pcm != nullptr, &F, &msg);   // ComputeSTFTWithWindow's checks first
@@ -417,7 +424,7 @@ int sonar_hpcp(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, 
   // (frame f of the signal is frame f - f0 of the samples from f0 * hop on: every frame lies inside
   // the signal), then the profile of its rows; both are queued on the context's stream, so the
   // scratch is reused in stream order and the host waits once, at the end.
-  const int64_t cf = chunk_frames_for(window_size);
+  const int64_t cf = magnitude_chunk_frames(window_size);
   double* scratch = o.tmp<double>("chunk", (size_t)std::min(cf, F) * (size_t)K);
   if (!scratch) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (HPCP magnitude scratch)");
   for (int64_t f0 = 0; p.size > 0 && f0 < F; f0 += cf) {

@@ -555,6 +555,31 @@ struct HpcpArgs {
 };
 int launch_hpcp(const HpcpArgs& a, hipStream_t s);   // -1: a shape the kernel does not take
 
+// HarmonicProduct per spectrum row (hps_kernels.hip; harmonic/harmonic_product.go): ComputeHPS or
+// ComputeHPSWithInterpolation, findF0Peak over [min_bin, max_bin], the bin's frequency and, when
+// asked for, ComputeHarmonicStrength and ComputeHarmonicity at that frequency.
+constexpr int HPS_MAX_K = HPCP_MAX_K;   // the row's powers live in LDS: 8 K bytes
+constexpr int HPS_MAX_HARMONICS = 64;   // one lane per harmonic strength
+struct HpsArgs {
+  const double* mag;             // F x K
+  int64_t F;
+  int K;
+  int nh;                        // numHarmonics; <= 1: the HPS is the power spectrum
+  int min_bin, max_bin;          // findF0Peak's scan range after its clamps (sonar_hps_bins)
+  double freq_res;               // float64(sampleRate) / float64(signalLength)
+  int interpolated;              // ComputeHPSWithInterpolation feeds the peak search
+  int32_t* f0_bin;               // [F]
+  double* f0;                    // [F]
+  double* confidence;            // [F] or null: the total-energy chain is not run
+  double* strengths;             // [F x nh] or null
+  double* hps;                   // [F x K] or null: only the scan range is evaluated
+  // sum of mag^2 in bin order per row from launch_hps_energy, or null: lane 0 walks the row in LDS
+  const double* total;
+};
+int launch_hps(const HpsArgs& a, hipStream_t s);   // -1: a shape the kernel does not take
+// total[f] = sum of mag[f][i]^2 in bin order, a row per lane (64 rows per wave, tiles through LDS)
+int launch_hps_energy(const double* mag, int64_t F, int K, double* total, hipStream_t s);
+
 // KeyEstimator over a chromagram (key_kernels.hip; algorithms/tonal/key_estimation.go).
 // AnalyzeKeyTransition's transition type (:843-872), shared by sonar_key_transition and the
 // transition records of sonar_key_batch.  Go's % keeps the dividend's sign, as C's does.

@@ -667,7 +667,7 @@ int fp_check(const sonar_fp_cfg* cfg, int64_t n, bool have_pcm, int64_t* F, std:
 // pcm_dev: pcm is already device memory even though the outputs are host buffers
 // (cfg->device_ptrs == 0) -- the sonar_fingerprint_f64le path (ingest_api.cpp)
 int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cfg* cfg, sonar_fp_out* out,
-                     bool pcm_dev, int64_t f_lo, int64_t f_hi) {
+                     bool pcm_dev, int64_t f_lo, int64_t f_hi, bool raw_window) {
   if (!c || !cfg || !out) return fail(c, SONAR_ERR_INVALID, "null argument");
   // ComputeSTFTWithWindow validation order (spectral.go:386-412), then the GPU path's limits
   int64_t F = 0;
@@ -741,14 +741,14 @@ int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cf
   c->last_fp_kernel = "";
   if (generic) {
     char key[512];
-    std::snprintf(key, sizeof(key), "gen|%d|%d|%d|%d|%d|%d|%.17g|%.17g|%d|%.17g", W, cfg->window_type,
+    std::snprintf(key, sizeof(key), "gen|%d|%d|%d|%d|%d|%d|%.17g|%.17g|%d|%.17g%s", W, cfg->window_type,
                   cfg->sample_rate, cfg->n_mfcc, cfg->n_filters, cfg->filterbank, cfg->low_freq, cfg->high_freq,
-                  cfg->use_lifter, cfg->lifter);
+                  cfg->use_lifter, cfg->lifter, raw_window ? "|raw" : "");
     auto it = c->fp_tables.find(key);
     if (it == c->fp_tables.end()) {
       FpTables t;
       std::vector<double> win;
-      if (!sonar::host::make_window(cfg->window_type, W, true, true, kStftBeta, kStftAlpha, win))
+      if (!sonar::host::make_window(cfg->window_type, W, true, !raw_window, kStftBeta, kStftAlpha, win))
         return fail(c, SONAR_ERR_INVALID, "failed to generate window: unsupported window type");
       std::vector<double> trig(2 * (size_t)W);
       for (int m = 0; m < W; ++m) {
@@ -856,14 +856,14 @@ int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cf
     for (int d = 0; d < 9; d++) p.out_spec[d] = d_spec[d];
     // tables, cached per configuration
     char key[512];
-    std::snprintf(key, sizeof(key), "%d|%d|%d|%d|%d|%d|%.17g|%.17g|%d|%.17g|%d|%d", W, cfg->window_type,
+    std::snprintf(key, sizeof(key), "%d|%d|%d|%d|%d|%d|%.17g|%.17g|%d|%.17g|%d|%d%s", W, cfg->window_type,
                   cfg->sample_rate, cfg->n_mfcc, cfg->n_filters, cfg->filterbank, cfg->low_freq, cfg->high_freq,
-                  cfg->use_lifter, cfg->lifter, (int)f64, NB);
+                  cfg->use_lifter, cfg->lifter, (int)f64, NB, raw_window ? "|raw" : "");
     auto it = c->fp_tables.find(key);
     if (it == c->fp_tables.end()) {
       FpTables t;
       std::vector<double> win;
-      if (!sonar::host::make_window(cfg->window_type, W, true, true, kStftBeta, kStftAlpha, win))
+      if (!sonar::host::make_window(cfg->window_type, W, true, !raw_window, kStftBeta, kStftAlpha, win))
         return fail(c, SONAR_ERR_INVALID, "failed to generate window: unsupported window type");
       t.window = upload_real(win, f64);
       sonar::host::MfccTables mt;

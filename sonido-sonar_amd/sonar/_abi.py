@@ -308,6 +308,13 @@ def lib():
     L.sonar_hpcp_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p, _i64p]
     L.sonar_hpcp.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HpcpParams),
                              _vp, _vp, _vp, C.c_int32]
+    L.sonar_hps_bins.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _i32p, _i32p]
+    L.sonar_hps_optimal_harmonics.argtypes = [C.c_int32, C.c_double, _i32p]
+    L.sonar_hps_from_spectrum.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                          C.c_double, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32]
+    L.sonar_hps_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p, _i64p]
+    L.sonar_hps.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                            C.c_int32, _vp, _vp, _vp, _vp, _vp, _i64p, C.c_int32]
     L.sonar_key_params_default.argtypes = [C.POINTER(KeyParams)]
     L.sonar_key_params_default.restype = None
     _key = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(KeyParams)]
@@ -674,6 +681,44 @@ def hpcp_plan(n, window_size, hop_size):
     if rc != OK:
         raise SonarError(rc, _HPCP_PLAN_ERRORS.get(rc, "sonar_hpcp_plan"))
     return dict(zip(("frames", "chunk_frames", "n_chunks"), [x.value for x in v]))
+
+
+_HPS_ERRORS = {ERR_UNSUPPORTED: "harmonic product: parameters the library does not reproduce (include/sonar_gpu.h)",
+               ERR_INVALID: "harmonic product: invalid argument"}
+
+
+def hps_bins(sample_rate, window_size, K, min_f0=80.0, max_f0=2000.0):
+    """sonar_hps_bins (host only): findF0Peak's scan range for rows of K bins -> (min_bin, max_bin);
+    min_bin > max_bin is an empty range."""
+    lo, hi = C.c_int32(), C.c_int32()
+    rc = lib().sonar_hps_bins(int(sample_rate), int(window_size), int(K), float(min_f0), float(max_f0), C.byref(lo),
+                              C.byref(hi))
+    if rc != OK:
+        raise SonarError(rc, _HPS_ERRORS.get(rc, "sonar_hps_bins"))
+    return lo.value, hi.value
+
+
+def hps_optimal_harmonics(sample_rate, min_f0):
+    """sonar_hps_optimal_harmonics (host only): HarmonicProduct.GetOptimalNumHarmonics."""
+    v = C.c_int32()
+    rc = lib().sonar_hps_optimal_harmonics(int(sample_rate), float(min_f0), C.byref(v))
+    if rc != OK:
+        raise SonarError(rc, _HPS_ERRORS.get(rc, "sonar_hps_optimal_harmonics"))
+    return v.value
+
+
+def hps_plan(n, window_size, hop_size):
+    """sonar_hps_plan (host only): how Context.hps splits its frames -> dict of frames, chunk_frames,
+    n_chunks."""
+    v = [C.c_int64() for _ in range(3)]
+    rc = lib().sonar_hps_plan(int(n), int(window_size), int(hop_size), *[C.byref(x) for x in v])
+    if rc != OK:
+        raise SonarError(rc, "window size below 2" if rc == ERR_UNSUPPORTED and 0 < int(window_size) < 2
+                         else _HPCP_PLAN_ERRORS.get(rc, "sonar_hps_plan"))
+    return dict(zip(("frames", "chunk_frames", "n_chunks"), [x.value for x in v]))
+
+
+_HPS_OPTIONAL = ("confidence", "strengths", "hps")
 
 
 def multi_shard(n, W, H, n_shards, shard):
@@ -1113,6 +1158,73 @@ class Context:
         wt = WINDOWS[window_type] if isinstance(window_type, str) else int(window_type)
         self._check(self._L.sonar_hpcp(self._h, pcm_ptr, int(n), int(sample_rate), int(window_size), int(hop_size), wt,
                                        C.byref(p), hpcp_ptr, energy_ptr, entropy_ptr, 1))
+
+    def hps_from_spectrum(self, mag, window_size, sample_rate, num_harmonics=10, min_f0=80.0, max_f0=2000.0,
+                          interpolated=False, skip=("hps",)):
+        """NewHarmonicProduct(sample_rate, num_harmonics, min_f0, max_f0) on every row of mag (F x K) with
+        signalLength window_size (sonar_hps_from_spectrum; the defaults are MusicFeatureExtractor's):
+        ComputeHPS (ComputeHPSWithInterpolation when interpolated), findF0Peak, the harmonic strengths
+        and the harmonicity -> dict of f0_bin (F, int32), f0, confidence (F), strengths (F x
+        num_harmonics) and hps (F x K); a name of confidence, strengths, hps in skip is passed as NULL
+        and comes back None."""
+        mag = _f64(mag)
+        mag = mag[None, :] if mag.ndim == 1 else mag
+        F, K = mag.shape
+        shapes = {"confidence": (F,), "strengths": (F, max(int(num_harmonics), 0)), "hps": (F, K)}
+        o = {"f0_bin": np.zeros(F, np.int32), "f0": np.zeros(F)}
+        o.update({k: None if k in skip else np.zeros(shapes[k]) for k in _HPS_OPTIONAL})
+        self._check(self._L.sonar_hps_from_spectrum(self._h, _ptr(mag) if mag.size else None, F, K, int(window_size),
+                                                    int(sample_rate), int(num_harmonics), float(min_f0), float(max_f0),
+                                                    int(bool(interpolated)), _ptr(o["f0_bin"]) if F else None,
+                                                    _ptr(o["f0"]) if F else None, *[_ptr(o[k]) for k in _HPS_OPTIONAL], 0))
+        return o
+
+    def hps_from_spectrum_device(self, mag_ptr, F, K, window_size, sample_rate, f0_bin_ptr, f0_ptr, num_harmonics=10,
+                                 min_f0=80.0, max_f0=2000.0, interpolated=False, confidence_ptr=None,
+                                 strengths_ptr=None, hps_ptr=None):
+        """hps_from_spectrum on device memory (device_ptrs = 1): mag (F x K), f0_bin (F int32), f0 (F) and
+        the optional confidence (F), strengths (F x num_harmonics) and hps (F x K) are device addresses."""
+        self._check(self._L.sonar_hps_from_spectrum(self._h, mag_ptr, int(F), int(K), int(window_size), int(sample_rate),
+                                                    int(num_harmonics), float(min_f0), float(max_f0),
+                                                    int(bool(interpolated)), f0_bin_ptr, f0_ptr, confidence_ptr,
+                                                    strengths_ptr, hps_ptr, 1))
+
+    def hps(self, pcm, sample_rate, window_size=2048, hop_size=512, num_harmonics=10, min_f0=80.0, max_f0=2000.0,
+            interpolated=False, skip=("magnitude",)):
+        """HarmonicProduct.EstimateF0WithConfidence on every frame of window_size samples at hop_size
+        (sonar_hps: applyWindow's unnormalised symmetric Hann, the float64 transform, the rows in a
+        bounded device scratch, hps_plan's chunks) -> dict of f0_bin, f0, confidence (frames), strengths
+        (frames x num_harmonics) and magnitude (frames x K, the rows the estimates were made on); a
+        name of confidence, strengths, magnitude in skip is passed as NULL and comes back None."""
+        pcm = _f64(pcm)
+        n = len(pcm)
+        v = [C.c_int64() for _ in range(3)]
+        F = 0
+        if self._L.sonar_hps_plan(n, int(window_size), int(hop_size), *[C.byref(x) for x in v]) == OK:
+            F = v[0].value                                  # otherwise the call below reports the error
+        shapes = {"confidence": (F,), "strengths": (F, max(int(num_harmonics), 0)),
+                  "magnitude": (F, int(window_size) // 2 + 1)}
+        o = {"f0_bin": np.zeros(F, np.int32), "f0": np.zeros(F)}
+        o.update({k: None if k in skip else np.zeros(shapes[k]) for k in shapes})
+        frames = C.c_int64()
+        self._check(self._L.sonar_hps(self._h, _ptr(pcm) if n else None, n, int(sample_rate), int(window_size),
+                                      int(hop_size), int(num_harmonics), float(min_f0), float(max_f0),
+                                      int(bool(interpolated)), _ptr(o["f0_bin"]), _ptr(o["f0"]),
+                                      *[_ptr(o[k]) for k in shapes], C.byref(frames), 0))
+        assert frames.value == F
+        return o
+
+    def hps_device(self, pcm_ptr, n, sample_rate, f0_bin_ptr, f0_ptr, window_size=2048, hop_size=512, num_harmonics=10,
+                   min_f0=80.0, max_f0=2000.0, interpolated=False, confidence_ptr=None, strengths_ptr=None,
+                   magnitude_ptr=None):
+        """hps on device memory (device_ptrs = 1): pcm (n doubles), f0_bin, f0 and the optional confidence,
+        strengths and magnitude are device addresses sized by hps_plan's frames, which is returned."""
+        frames = C.c_int64()
+        self._check(self._L.sonar_hps(self._h, pcm_ptr, int(n), int(sample_rate), int(window_size), int(hop_size),
+                                      int(num_harmonics), float(min_f0), float(max_f0), int(bool(interpolated)),
+                                      f0_bin_ptr, f0_ptr, confidence_ptr, strengths_ptr, magnitude_ptr,
+                                      C.byref(frames), 1))
+        return frames.value
 
     def key_frames(self, chroma, params=None, skip=()):
         """KeyEstimator.EstimateKey on every row of chroma (F x dim) (sonar_key_frames; params:
