@@ -43,7 +43,17 @@
  *   sonar_hps_bins             <- findF0Peak's scan range (:128-139)
  *   sonar_hps_optimal_harmonics <- HarmonicProduct.GetOptimalNumHarmonics (:301-314)
  *   sonar_hps_plan             <- the frame count and the chunks sonar_hps works in
- *   sonar_key_frames           <- KeyEstimator.EstimateKey / EstimateKeyFromHPCP per chroma row,
+ *   sonar_spectral_flux        <- SpectralFlux.Compute / ComputeAllChanges (algorithms/spectral/spectral_flux.go:17-56)
+ *   sonar_rms_envelope         <- Envelope.ComputeRMS (algorithms/temporal/envelope.go:18-43)
+ *   sonar_onset_peaks          <- OnsetDetection.findFluxPeaks on any curve (algorithms/temporal/onset_detection.go:97-120)
+ *   sonar_onset_adaptive_threshold <- OnsetDetection.AdaptiveThreshold (:200-222)
+ *   sonar_onsets_flux          <- OnsetDetection.DetectOnsets (:26-56)
+ *   sonar_onsets_energy        <- OnsetDetection.DetectOnsetsEnergy (:59-94)
+ *   sonar_onsets_complex       <- OnsetDetection.DetectOnsetsComplex, combineOnsets, ComputeOnsetDensity (:123-197)
+ *   sonar_tempo_from_onsets    <- TempoEstimation.findTempoFromIntervals (algorithms/temporal/tempo_estimation.go:77-118)
+ *   sonar_tempo_autocorrelation <- TempoEstimation.EstimateTempoAutocorrelation (:51-74, :121-201)
+ *   sonar_tempo                <- TempoEstimation.EstimateTempo, EstimateTempoRange, ClassifyTempoCategory (:22-48, :204-232)
+ *   sonar_key_frames          <- KeyEstimator.EstimateKey / EstimateKeyFromHPCP per chroma row,
  *                                 KeyEstimationBatch.ProcessBatch (algorithms/tonal/key_estimation.go:196-247, 911)
  *   sonar_key_sequence         <- KeyEstimator.EstimateKeySequence (key_estimation.go:250-270)
  *   sonar_key_batch            <- KeyEstimationBatch.ProcessBatch / GetGlobalKey / GetKeyProgression (:896-1005)
@@ -617,6 +627,140 @@ int sonar_hps(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate,
               int32_t* f0_bin, double* f0, double* confidence /* or NULL */, double* strengths /* or NULL */,
               double* magnitude /* frames x K or NULL */, int64_t* frames /* host, or NULL */,
               int32_t device_ptrs);
+
+/* ---- onsets and tempo (float64) ---------------------------------------------
+ * OnsetDetection (algorithms/temporal/onset_detection.go) and TempoEstimation (tempo_estimation.go)
+ * over SpectralFlux (algorithms/spectral/spectral_flux.go) and Envelope.ComputeRMS (temporal/envelope.go).
+ * Every sum keeps the reference's order and nothing is fused, so the curves are the reference's bit for
+ * bit and the decisions made on them (strict maxima, thresholds, votes) are the reference's.  Frame
+ * indices, onset samples and counts are int64.  A count, a frame count and a curve length are written
+ * to host memory whatever device_ptrs says; arrays (and sonar_tempo_autocorrelation's two scalars)
+ * follow device_ptrs.  DESIGN.md F70-F79 list what the reference does that a reader would not guess.
+ * Not reproduced (SONAR_ERR_UNSUPPORTED, the message says which): sample_rate <= 0; hop_size <= 0 where
+ * a minimum interval is converted; a min_interval whose frame count is NaN or does not fit an int32
+ * (Go's conversion is implementation-defined there); rows of more than 8192 bins. */
+#define SONAR_ONSET_WINDOW 1024        /* DetectOnsets' windowSize (onset_detection.go:32)       */
+#define SONAR_ONSET_HOP 512            /* ... and hopSize (:33)                                   */
+#define SONAR_ONSET_ENERGY_FRAME 512   /* DetectOnsetsEnergy's frameSize (:65)                    */
+#define SONAR_ONSET_ENERGY_HOP 256     /* ... and hopSize (:66)                                   */
+/* SpectralFlux.Compute (spectral_flux.go:17-36), or ComputeAllChanges (:39-56) when all_changes != 0, on
+ * F rows of K magnitudes: flux[t] = sqrt(sum over bins, ascending, of d * d), d = mag[t+1][f] - mag[t][f];
+ * Compute adds a term only when d > 0, so a NaN difference adds nothing there.  max(F - 1, 0) values;
+ * F < 2 writes nothing. */
+int sonar_spectral_flux(sonar_ctx* ctx, const double* mag /* F x K */, int64_t F, int32_t K, int32_t all_changes,
+                        double* flux /* max(F-1,0) */, int32_t device_ptrs);
+/* len(Envelope.ComputeRMS(signal of n, frame_size, hop_size)), host only: (n - frame_size) / hop_size + 1,
+ * and 0 when n < frame_size, frame_size <= 0 or hop_size <= 0 (envelope.go:19-23). */
+int64_t sonar_rms_envelope_frames(int64_t n, int32_t frame_size, int32_t hop_size);
+/* Envelope.ComputeRMS (envelope.go:18-43): env[i] = sqrt((sum of x[j] * x[j] over the frame, in sample
+ * order) / float64(frame_size)).  frames (host, or NULL) receives sonar_rms_envelope_frames' value; an
+ * empty result is SONAR_OK. */
+int sonar_rms_envelope(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t frame_size, int32_t hop_size,
+                       double* env, int64_t* frames /* host, or NULL */, int32_t device_ptrs);
+/* The most peaks findFluxPeaks can return on n values, host only: max((n - 1) / 2, 0) (strict local
+ * maxima inside 1 .. n - 2 are two apart). */
+int64_t sonar_onset_peaks_width(int64_t n);
+/* findFluxPeaks' minIntervalFrames, host only: int(min_interval * float64(sample_rate) /
+ * float64(hop_size)), truncating (:103). */
+int sonar_onset_min_interval_frames(double min_interval, int32_t sample_rate, int32_t hop_size, int32_t* frames);
+/* findFluxPeaks (onset_detection.go:97-120) on any curve of n values: index i in 1 .. n - 2 is kept when
+ * v[i] > v[i-1], v[i] > v[i+1], v[i] >= threshold and i - last >= minIntervalFrames, where last is the
+ * index kept before (-minIntervalFrames at the start): a serial greedy over the strict local maxima.  A
+ * NaN value or threshold makes its comparisons false; a non-positive minIntervalFrames never rejects.
+ * index has sonar_onset_peaks_width(n) slots, the kept indices ascending, the slots past count 0.
+ * n < 3 -> SONAR_OK, count 0, before anything else is looked at. */
+int sonar_onset_peaks(sonar_ctx* ctx, const double* curve, int64_t n, double threshold, double min_interval,
+                      int32_t hop_size, int32_t sample_rate, int64_t* index /* width */,
+                      int64_t* count /* host */, int32_t device_ptrs);
+/* AdaptiveThreshold (:200-222): mean + 2 * population standard deviation, two passes in index order;
+ * 0 for n == 0. */
+int sonar_onset_adaptive_threshold(sonar_ctx* ctx, const double* curve, int64_t n, double* value,
+                                   int32_t device_ptrs);
+/* DetectOnsets (:26-56): the magnitudes of the STFT with no window at all (a nil window, stft.go:112),
+ * SpectralFlux.Compute over them, findFluxPeaks on the flux, onset sample = index in the flux array *
+ * hop_size (flux index i compares frames i and i + 1 and is reported as i).
+ * window_size / hop_size 0 are the reference's SONAR_ONSET_WINDOW / SONAR_ONSET_HOP; other values are
+ * the same algorithm on another grid, with sonar_hpcp's window sizes.  The rows go through the
+ * bounded device scratch of sonar_hpcp, chunk_frames at a time (sonar_hpcp_plan), the last row of a
+ * chunk carried into the next so that the flux at a seam is the whole spectrogram's.
+ * onsets has sonar_onset_peaks_width(frames - 1) slots (slots past count 0); flux (frames - 1 values) and
+ * magnitude (frames x K) may be NULL; frames (host, or NULL) receives the frame count.
+ * n == 0 -> SONAR_OK and nothing (:27-29); then sonar_fingerprint's errors (n <= window_size - hop_size:
+ * SONAR_ERR_TOO_SHORT "signal too short for given window size and hop size"; Go's truncating frame
+ * count gives window_size - hop_size < n < window_size one frame, left all zero); one
+ * frame -> no flux, no onsets, SONAR_OK. */
+int sonar_onsets_flux(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t window_size,
+                      int32_t hop_size, double threshold, double min_interval, int64_t* onsets,
+                      int64_t* count /* host */, double* flux /* or NULL */,
+                      double* magnitude /* frames x K or NULL */, int64_t* frames /* host, or NULL */,
+                      int32_t device_ptrs);
+/* DetectOnsetsEnergy (:59-94): ComputeRMS at frame_size / hop_size (0: SONAR_ONSET_ENERGY_FRAME /
+ * SONAR_ONSET_ENERGY_HOP), energyDiff[i] = env[i+1] - env[i] when that is > 0 and else 0 (a NaN
+ * difference gives 0), findFluxPeaks, onset sample = i * hop_size.  curve (the energyDiff, n_curve =
+ * max(frames - 1, 0) values, or NULL); onsets has sonar_onset_peaks_width(n_curve) slots.  A signal
+ * shorter than a frame gives nothing and no error. */
+int sonar_onsets_energy(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t frame_size,
+                        int32_t hop_size, double threshold, double min_interval, int64_t* onsets,
+                        int64_t* count /* host */, double* curve /* or NULL */, int64_t* n_curve /* host, or NULL */,
+                        int32_t device_ptrs);
+/* The slots sonar_onsets_complex needs for n samples, host only: the two detectors' widths added. */
+int64_t sonar_onsets_complex_width(int64_t n);
+/* DetectOnsetsComplex (:123-146): DetectOnsets at threshold 0.3 and DetectOnsetsEnergy at 0.1, both with
+ * a 0.05 s minimum interval, concatenated, sorted ascending, and a value dropped when it lies within
+ * int(0.05 * float64(sample_rate)) samples of one already kept (combineOnsets :149-182).  density (host,
+ * or NULL) is ComputeOnsetDensity (:185-197): count / (n / sample_rate), 0 when n == 0.  The flux
+ * detector's error ends the call even where the energy detector would have run (:135-137). */
+int sonar_onsets_complex(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int64_t* onsets,
+                         int64_t* count /* host */, double* density /* host, or NULL */, int32_t device_ptrs);
+/* EstimateTempo's tail (tempo_estimation.go:33-47) and findTempoFromIntervals (:77-118) over a list of
+ * onset samples, host only: intervals between consecutive onsets in seconds; one strictly inside
+ * (0.2, 2.0) votes for the first bin of {60, 70, ..., 180, 200} nearest to 60 / interval when that
+ * distance is strictly below 10; the most voted bin wins, the lowest of equals; 120 when nothing voted,
+ * 0 with fewer than two onsets.  bin_counts (14 values, or NULL) receives the votes. */
+int sonar_tempo_from_onsets(const int64_t* onsets, int64_t count, int32_t sample_rate, double* tempo,
+                            int32_t* bin_counts /* 14, or NULL */);
+/* EstimateTempoAutocorrelation's integer side, host only: frame_size = int(0.1 * float64(sample_rate)),
+ * hop_size = frame_size / 4, the envelope's length, n_autocorr = envelope_len / 2 (0 when the envelope
+ * has fewer than 10 values, :62) and, when n_autocorr >= 10, the search's lag range after its clamps
+ * (:166-174). */
+int sonar_tempo_autocorr_plan(int64_t n, int32_t sample_rate, int32_t* frame_size, int32_t* hop_size,
+                              int64_t* envelope_len, int64_t* n_autocorr, int64_t* min_lag, int64_t* max_lag);
+/* EstimateTempoAutocorrelation (:51-74): the RMS envelope e at the plan's frame and hop;
+ * calculateAutocorrelation (:121-150), ac[lag] = (sum over ascending i of e[i] * e[i+lag]) / float64(len -
+ * lag) for lag < len / 2, then the loop `ac[i] /= ac[0]` from i = 0 when ac[0] > 0, which makes ac[0] its
+ * own quotient first and divides every other lag by that: the curve stays unnormalised;
+ * findTempoFromAutocorrelation (:153-201), the highest strict local maximum above 0.0 inside the lag
+ * range, the first of equals, tempo = 60 / (float64(lag) * (float64(hop) / float64(sample_rate))), 120
+ * with no maximum, 0 when the envelope has fewer than 10 values or the curve fewer than 10 lags.
+ * autocorr == NULL: only lag 0 and the lags the search reads are computed.  With a buffer of
+ * n_autocorr values (sonar_tempo_autocorr_plan) the whole curve is computed as well; tempo and best_lag
+ * are the same either way.  tempo and best_lag (or NULL) follow device_ptrs; n_autocorr is host. */
+int sonar_tempo_autocorrelation(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, double* tempo,
+                                int64_t* best_lag, double* autocorr /* n_autocorr, or NULL */,
+                                int64_t* n_autocorr /* host, or NULL */, int32_t device_ptrs);
+/* ClassifyTempoCategory (:220-232): cut at 60 / 90 / 120 / 150 */
+enum {
+  SONAR_TEMPO_VERY_SLOW = 0, SONAR_TEMPO_SLOW, SONAR_TEMPO_MODERATE, SONAR_TEMPO_FAST, SONAR_TEMPO_VERY_FAST
+};
+int32_t sonar_tempo_category(double tempo);
+/* "very_slow", "slow", "moderate", "fast", "very_fast"; "" for anything else */
+const char* sonar_tempo_category_name(int32_t category);
+typedef struct sonar_tempo_result {
+  double onset_tempo;      /* EstimateTempo; 0 when its error was dropped (see onset_error)         */
+  double autocorr_tempo;   /* EstimateTempoAutocorrelation                                         */
+  double tempo;            /* EstimateTempoRange: (onset_tempo + autocorr_tempo) / 2               */
+  double confidence;       /* math.Max(0, 1 - difference / 50)                                     */
+  double difference;       /* |onset_tempo - autocorr_tempo|                                       */
+  int64_t onset_count;     /* len(DetectOnsetsComplex)                                             */
+  int64_t best_lag;        /* the autocorrelation's lag, 0 when there was none                     */
+  int32_t category;        /* SONAR_TEMPO_* of tempo                                               */
+  int32_t onset_error;     /* SONAR_OK, or the SONAR_ERR_TOO_SHORT EstimateTempoRange drops (:206) */
+} sonar_tempo_result;
+/* EstimateTempo (:22-48), EstimateTempoAutocorrelation, EstimateTempoRange (:204-217) and
+ * ClassifyTempoCategory of the average, with the samples staged once.  result is host memory;
+ * device_ptrs speaks of pcm.  n == 0 is no error: both tempos are 0 and the confidence 1. */
+int sonar_tempo(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, sonar_tempo_result* result,
+                int32_t device_ptrs);
 
 /* ---- key estimation over a chromagram (float64) ----------------------------
  * KeyEstimator (algorithms/tonal/key_estimation.go) on F rows of dim chroma values, for example the

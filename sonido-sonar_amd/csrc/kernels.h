@@ -580,6 +580,30 @@ int launch_hps(const HpsArgs& a, hipStream_t s);   // -1: a shape the kernel doe
 // total[f] = sum of mag[f][i]^2 in bin order, a row per lane (64 rows per wave, tiles through LDS)
 int launch_hps_energy(const double* mag, int64_t F, int K, double* total, hipStream_t s);
 
+// OnsetDetection and TempoEstimation (onset_kernels.hip; algorithms/temporal/onset_detection.go,
+// tempo_estimation.go, spectral/spectral_flux.go, temporal/envelope.go).  Every launcher returns 0,
+// -1 for arguments the kernel does not take or -5 for a failed launch.
+constexpr int ONSET_MAX_K = HPCP_MAX_K;
+// flux[t] = sqrt(sum over bins of d^2), d = mag[t+1][f] - mag[t][f], in bin order; only d > 0 unless
+// all_changes.  F - 1 values; F < 2 launches nothing.
+int launch_onset_flux(const double* mag, int64_t F, int K, bool all_changes, double* flux, hipStream_t s);
+// env[f] = sqrt(sum of x[f * hop + j]^2 over j < frame, in sample order, / float64(frame))
+int launch_onset_rms(const double* x, int64_t frames, int frame, int hop, double* env, hipStream_t s);
+// diff[i] = env[i+1] - env[i] when that is > 0, else 0, for i < n (env holds n + 1 values)
+int launch_onset_posdiff(const double* env, int64_t n, double* diff, hipStream_t s);
+// findFluxPeaks on n values: mask is scratch of onset_mask_words(n) words; index[k] = frame * scale for
+// the kept frames in order (at most width of them are written), *count = how many were kept
+int64_t onset_mask_words(int64_t n);
+int launch_onset_peaks(const double* v, int64_t n, double threshold, int32_t min_interval_frames, int64_t scale,
+                       uint64_t* mask, int64_t* index, int64_t width, int64_t* count, hipStream_t s);
+// AdaptiveThreshold of n >= 1 values
+int launch_onset_threshold(const double* v, int64_t n, double* value, hipStream_t s);
+// the unnormalised autocorrelation of L envelope values at nlags lags from lag_lo on (zero_first: lag 0
+// first, then lag_lo, lag_lo + 1, ...), and the reference's normalisation of a whole curve
+int launch_onset_autocorr(const double* e, int64_t L, int64_t lag_lo, int64_t nlags, bool zero_first, double* raw,
+                          hipStream_t s);
+int launch_onset_autocorr_norm(const double* raw, int64_t n, double* ac, hipStream_t s);
+
 // KeyEstimator over a chromagram (key_kernels.hip; algorithms/tonal/key_estimation.go).
 // AnalyzeKeyTransition's transition type (:843-872), shared by sonar_key_transition and the
 // transition records of sonar_key_batch.  Go's % keeps the dividend's sign, as C's does.

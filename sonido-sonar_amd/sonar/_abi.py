@@ -75,6 +75,18 @@ class HpcpParams(C.Structure):
 HPCP_WEIGHTS = {"none": 0, "cosine": 1, "squared_cosine": 2}
 
 
+class TempoResult(C.Structure):
+    """sonar_tempo_result: EstimateTempo, EstimateTempoAutocorrelation, EstimateTempoRange and
+    ClassifyTempoCategory of one signal (tempo_estimation.go)."""
+    _fields_ = [(n, C.c_double) for n in ("onset_tempo", "autocorr_tempo", "tempo", "confidence", "difference")] + \
+               [("onset_count", C.c_int64), ("best_lag", C.c_int64), ("category", C.c_int32), ("onset_error", C.c_int32)]
+
+
+# ClassifyTempoCategory's names by SONAR_TEMPO_* code; DetectOnsets' and DetectOnsetsEnergy's grids
+TEMPO_CATEGORIES = ["very_slow", "slow", "moderate", "fast", "very_fast"]
+ONSET_WINDOW, ONSET_HOP, ONSET_ENERGY_FRAME, ONSET_ENERGY_HOP = 1024, 512, 512, 256
+
+
 class KeyParams(C.Structure):
     """sonar_key_params: the fields of KeyEstimationParams the reference reads (key_estimation.go:88-113)."""
     _fields_ = [(n, C.c_int32) for n in ("profile", "hpcp_size", "normalize_chroma", "remove_mean", "binary_mode",
@@ -315,6 +327,31 @@ def lib():
     L.sonar_hps_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p, _i64p]
     L.sonar_hps.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                             C.c_int32, _vp, _vp, _vp, _vp, _vp, _i64p, C.c_int32]
+    L.sonar_spectral_flux.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int32]
+    L.sonar_rms_envelope_frames.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.sonar_rms_envelope_frames.restype = C.c_int64
+    L.sonar_rms_envelope.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _i64p, C.c_int32]
+    L.sonar_onset_peaks_width.argtypes = [C.c_int64]
+    L.sonar_onset_peaks_width.restype = C.c_int64
+    L.sonar_onset_min_interval_frames.argtypes = [C.c_double, C.c_int32, C.c_int32, _i32p]
+    L.sonar_onset_peaks.argtypes = [_vp, _vp, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, _i64p,
+                                    C.c_int32]
+    L.sonar_onset_adaptive_threshold.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int32]
+    L.sonar_onsets_flux.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _vp,
+                                    _i64p, _vp, _vp, _i64p, C.c_int32]
+    L.sonar_onsets_energy.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _vp,
+                                      _i64p, _vp, _i64p, C.c_int32]
+    L.sonar_onsets_complex_width.argtypes = [C.c_int64]
+    L.sonar_onsets_complex_width.restype = C.c_int64
+    L.sonar_onsets_complex.argtypes = [_vp, _vp, C.c_int64, C.c_int32, _vp, _i64p, _d, C.c_int32]
+    L.sonar_tempo_from_onsets.argtypes = [_vp, C.c_int64, C.c_int32, _d, _i32p]
+    L.sonar_tempo_autocorr_plan.argtypes = [C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i64p, _i64p]
+    L.sonar_tempo_autocorrelation.argtypes = [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _i64p, C.c_int32]
+    L.sonar_tempo_category.argtypes = [C.c_double]
+    L.sonar_tempo_category.restype = C.c_int32
+    L.sonar_tempo_category_name.argtypes = [C.c_int32]
+    L.sonar_tempo_category_name.restype = C.c_char_p
+    L.sonar_tempo.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(TempoResult), C.c_int32]
     L.sonar_key_params_default.argtypes = [C.POINTER(KeyParams)]
     L.sonar_key_params_default.restype = None
     _key = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(KeyParams)]
@@ -719,6 +756,68 @@ def hps_plan(n, window_size, hop_size):
 
 
 _HPS_OPTIONAL = ("confidence", "strengths", "hps")
+
+
+_ONSET_ERRORS = {ERR_UNSUPPORTED: "onsets: parameters the library does not reproduce (include/sonar_gpu.h)",
+                 ERR_INVALID: "onsets: invalid argument"}
+
+
+def onset_peaks_width(n):
+    """sonar_onset_peaks_width (host only): the most peaks findFluxPeaks returns on n values."""
+    return int(lib().sonar_onset_peaks_width(int(n)))
+
+
+def rms_envelope_frames(n, frame_size, hop_size):
+    """sonar_rms_envelope_frames (host only): len(Envelope.ComputeRMS(...))."""
+    return int(lib().sonar_rms_envelope_frames(int(n), int(frame_size), int(hop_size)))
+
+
+def onsets_complex_width(n):
+    """sonar_onsets_complex_width (host only): the slots Context.onsets_complex needs for n samples."""
+    return int(lib().sonar_onsets_complex_width(int(n)))
+
+
+def onset_min_interval_frames(min_interval, sample_rate, hop_size):
+    """sonar_onset_min_interval_frames (host only): findFluxPeaks' minIntervalFrames."""
+    v = C.c_int32()
+    rc = lib().sonar_onset_min_interval_frames(float(min_interval), int(sample_rate), int(hop_size), C.byref(v))
+    if rc != OK:
+        raise SonarError(rc, _ONSET_ERRORS.get(rc, "sonar_onset_min_interval_frames"))
+    return v.value
+
+
+def tempo_from_onsets(onsets, sample_rate):
+    """sonar_tempo_from_onsets (host only): EstimateTempo's tail over a list of onset samples ->
+    (tempo, the 14 votes of findTempoFromIntervals' bins)."""
+    a = np.ascontiguousarray(onsets, dtype=np.int64)
+    t, counts = C.c_double(), np.zeros(14, np.int32)
+    rc = lib().sonar_tempo_from_onsets(_ptr(a) if a.size else None, int(a.size), int(sample_rate), C.byref(t),
+                                       counts.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != OK:
+        raise SonarError(rc, _ONSET_ERRORS.get(rc, "sonar_tempo_from_onsets"))
+    return t.value, counts
+
+
+def tempo_autocorr_plan(n, sample_rate):
+    """sonar_tempo_autocorr_plan (host only): EstimateTempoAutocorrelation's integer side -> dict of
+    frame_size, hop_size, envelope_len, n_autocorr, min_lag, max_lag."""
+    a, b = C.c_int32(), C.c_int32()
+    v = [C.c_int64() for _ in range(4)]
+    rc = lib().sonar_tempo_autocorr_plan(int(n), int(sample_rate), C.byref(a), C.byref(b), *[C.byref(x) for x in v])
+    if rc != OK:
+        raise SonarError(rc, _ONSET_ERRORS.get(rc, "sonar_tempo_autocorr_plan"))
+    return dict(frame_size=a.value, hop_size=b.value, envelope_len=v[0].value, n_autocorr=v[1].value,
+                min_lag=v[2].value, max_lag=v[3].value)
+
+
+def tempo_category(tempo):
+    """sonar_tempo_category (host only): ClassifyTempoCategory's SONAR_TEMPO_* code."""
+    return int(lib().sonar_tempo_category(float(tempo)))
+
+
+def tempo_category_name(category):
+    """sonar_tempo_category_name (host only)."""
+    return lib().sonar_tempo_category_name(int(category)).decode()
 
 
 def multi_shard(n, W, H, n_shards, shard):
@@ -1225,6 +1324,184 @@ class Context:
                                       f0_bin_ptr, f0_ptr, confidence_ptr, strengths_ptr, magnitude_ptr,
                                       C.byref(frames), 1))
         return frames.value
+
+    def spectral_flux(self, mag, all_changes=False):
+        """SpectralFlux.Compute (ComputeAllChanges when all_changes) over the rows of mag (F x K)
+        (sonar_spectral_flux) -> max(F - 1, 0) values."""
+        mag = _f64(mag)
+        F, K = mag.shape
+        flux = np.zeros(max(F - 1, 0))
+        self._check(self._L.sonar_spectral_flux(self._h, _ptr(mag) if mag.size else None, F, K, int(bool(all_changes)),
+                                                _ptr(flux) if flux.size else None, 0))
+        return flux
+
+    def spectral_flux_device(self, mag_ptr, F, K, flux_ptr, all_changes=False):
+        """spectral_flux on device memory (device_ptrs = 1): mag (F x K) and flux (F - 1) are device addresses."""
+        self._check(self._L.sonar_spectral_flux(self._h, mag_ptr, int(F), int(K), int(bool(all_changes)), flux_ptr, 1))
+
+    def rms_envelope(self, pcm, frame_size, hop_size):
+        """Envelope.ComputeRMS (sonar_rms_envelope) -> the envelope, empty where the reference's is."""
+        pcm = _f64(pcm)
+        env = np.zeros(rms_envelope_frames(len(pcm), frame_size, hop_size))
+        frames = C.c_int64()
+        self._check(self._L.sonar_rms_envelope(self._h, _ptr(pcm) if pcm.size else None, len(pcm), int(frame_size),
+                                               int(hop_size), _ptr(env) if env.size else None, C.byref(frames), 0))
+        assert frames.value == len(env)
+        return env
+
+    def rms_envelope_device(self, pcm_ptr, n, frame_size, hop_size, env_ptr):
+        """rms_envelope on device memory (device_ptrs = 1) -> the number of values written."""
+        frames = C.c_int64()
+        self._check(self._L.sonar_rms_envelope(self._h, pcm_ptr, int(n), int(frame_size), int(hop_size), env_ptr,
+                                               C.byref(frames), 1))
+        return frames.value
+
+    def onset_peaks(self, curve, threshold, min_interval, hop_size, sample_rate, padded=False):
+        """findFluxPeaks on any curve (sonar_onset_peaks) -> the kept indices (int64), or with padded the
+        whole onset_peaks_width(n) slots and the count."""
+        curve = _f64(curve)
+        n = len(curve)
+        index = np.full(onset_peaks_width(n), -1, np.int64)
+        count = C.c_int64(-1)
+        self._check(self._L.sonar_onset_peaks(self._h, _ptr(curve) if n else None, n, float(threshold),
+                                              float(min_interval), int(hop_size), int(sample_rate),
+                                              _ptr(index) if index.size else None, C.byref(count), 0))
+        return (index, count.value) if padded else index[:count.value]
+
+    def onset_peaks_device(self, curve_ptr, n, threshold, min_interval, hop_size, sample_rate, index_ptr):
+        """onset_peaks on device memory (device_ptrs = 1): curve (n) and index (onset_peaks_width(n) int64)
+        are device addresses -> the count."""
+        count = C.c_int64(-1)
+        self._check(self._L.sonar_onset_peaks(self._h, curve_ptr, int(n), float(threshold), float(min_interval),
+                                              int(hop_size), int(sample_rate), index_ptr, C.byref(count), 1))
+        return count.value
+
+    def onset_adaptive_threshold(self, curve):
+        """OnsetDetection.AdaptiveThreshold (sonar_onset_adaptive_threshold)."""
+        curve = _f64(curve)
+        v = np.full(1, -1.0)
+        self._check(self._L.sonar_onset_adaptive_threshold(self._h, _ptr(curve) if curve.size else None, len(curve),
+                                                           _ptr(v), 0))
+        return float(v[0])
+
+    def onset_adaptive_threshold_device(self, curve_ptr, n, value_ptr):
+        """onset_adaptive_threshold on device memory (device_ptrs = 1): curve (n) and value (a double)."""
+        self._check(self._L.sonar_onset_adaptive_threshold(self._h, curve_ptr, int(n), value_ptr, 1))
+
+    def onsets_flux(self, pcm, sample_rate, threshold, min_interval, window_size=0, hop_size=0, skip=("magnitude",)):
+        """OnsetDetection.DetectOnsets (sonar_onsets_flux; window_size / hop_size 0 are the reference's 1024 /
+        512) -> dict of onsets (samples, int64), flux (frames - 1), magnitude (frames x K, the unwindowed
+        STFT rows the flux was taken on) and frames; a name of flux, magnitude in skip is passed as NULL
+        and comes back None."""
+        pcm = _f64(pcm)
+        n = len(pcm)
+        W, H = int(window_size) or ONSET_WINDOW, int(hop_size) or ONSET_HOP
+        F = max(stft_frames(n, W, H), 0) if n > 0 and W > 0 and H > 0 else 0   # Go's truncating count
+        onsets = np.full(onset_peaks_width(F - 1), -1, np.int64)
+        o = {"flux": None if "flux" in skip else np.zeros(max(F - 1, 0)),
+             "magnitude": None if "magnitude" in skip else np.zeros((F, W // 2 + 1))}
+        count, frames = C.c_int64(), C.c_int64()
+        self._check(self._L.sonar_onsets_flux(self._h, _ptr(pcm) if n else None, n, int(sample_rate), int(window_size),
+                                              int(hop_size), float(threshold), float(min_interval),
+                                              _ptr(onsets) if onsets.size else None, C.byref(count),
+                                              _ptr(o["flux"]) if F > 1 else None, _ptr(o["magnitude"]) if F else None,
+                                              C.byref(frames), 0))
+        assert frames.value == F and not onsets[count.value:].any()
+        o.update(onsets=onsets[:count.value], frames=F)
+        return o
+
+    def onsets_flux_device(self, pcm_ptr, n, sample_rate, threshold, min_interval, onsets_ptr, window_size=0,
+                           hop_size=0, flux_ptr=None, magnitude_ptr=None):
+        """onsets_flux on device memory (device_ptrs = 1) -> (count, frames)."""
+        count, frames = C.c_int64(), C.c_int64()
+        self._check(self._L.sonar_onsets_flux(self._h, pcm_ptr, int(n), int(sample_rate), int(window_size),
+                                              int(hop_size), float(threshold), float(min_interval), onsets_ptr,
+                                              C.byref(count), flux_ptr, magnitude_ptr, C.byref(frames), 1))
+        return count.value, frames.value
+
+    def onsets_energy(self, pcm, sample_rate, threshold, min_interval, frame_size=0, hop_size=0):
+        """OnsetDetection.DetectOnsetsEnergy (sonar_onsets_energy; frame_size / hop_size 0 are the
+        reference's 512 / 256) -> dict of onsets (samples, int64) and curve (the energyDiff)."""
+        pcm = _f64(pcm)
+        n = len(pcm)
+        fs, hs = int(frame_size) or ONSET_ENERGY_FRAME, int(hop_size) or ONSET_ENERGY_HOP
+        nc = max(rms_envelope_frames(n, fs, hs) - 1, 0)
+        onsets, curve = np.full(onset_peaks_width(nc), -1, np.int64), np.zeros(nc)
+        count, ncurve = C.c_int64(), C.c_int64()
+        self._check(self._L.sonar_onsets_energy(self._h, _ptr(pcm) if n else None, n, int(sample_rate), int(frame_size),
+                                                int(hop_size), float(threshold), float(min_interval),
+                                                _ptr(onsets) if onsets.size else None, C.byref(count),
+                                                _ptr(curve) if nc else None, C.byref(ncurve), 0))
+        assert ncurve.value == nc and not onsets[count.value:].any()
+        return {"onsets": onsets[:count.value], "curve": curve}
+
+    def onsets_energy_device(self, pcm_ptr, n, sample_rate, threshold, min_interval, onsets_ptr, frame_size=0,
+                             hop_size=0, curve_ptr=None):
+        """onsets_energy on device memory (device_ptrs = 1) -> (count, the curve's length)."""
+        count, ncurve = C.c_int64(), C.c_int64()
+        self._check(self._L.sonar_onsets_energy(self._h, pcm_ptr, int(n), int(sample_rate), int(frame_size),
+                                                int(hop_size), float(threshold), float(min_interval), onsets_ptr,
+                                                C.byref(count), curve_ptr, C.byref(ncurve), 1))
+        return count.value, ncurve.value
+
+    def onsets_complex(self, pcm, sample_rate):
+        """OnsetDetection.DetectOnsetsComplex and ComputeOnsetDensity (sonar_onsets_complex) -> dict of
+        onsets (samples, int64) and density (onsets per second)."""
+        pcm = _f64(pcm)
+        n = len(pcm)
+        onsets = np.full(onsets_complex_width(n), -1, np.int64)
+        count, density = C.c_int64(), C.c_double()
+        self._check(self._L.sonar_onsets_complex(self._h, _ptr(pcm) if n else None, n, int(sample_rate),
+                                                 _ptr(onsets) if onsets.size else None, C.byref(count),
+                                                 C.byref(density), 0))
+        assert not onsets[count.value:].any()
+        return {"onsets": onsets[:count.value], "density": density.value}
+
+    def onsets_complex_device(self, pcm_ptr, n, sample_rate, onsets_ptr):
+        """onsets_complex on device memory (device_ptrs = 1): onsets has onsets_complex_width(n) int64 slots
+        -> (count, density)."""
+        count, density = C.c_int64(), C.c_double()
+        self._check(self._L.sonar_onsets_complex(self._h, pcm_ptr, int(n), int(sample_rate), onsets_ptr, C.byref(count),
+                                                 C.byref(density), 1))
+        return count.value, density.value
+
+    def tempo_autocorrelation(self, pcm, sample_rate, full=False):
+        """TempoEstimation.EstimateTempoAutocorrelation (sonar_tempo_autocorrelation) -> dict of tempo,
+        best_lag and autocorr: None, or with full the whole curve (tempo_autocorr_plan's n_autocorr
+        values) where the narrow form computes only the lags the peak search reads."""
+        pcm = _f64(pcm)
+        n = len(pcm)
+        nac = tempo_autocorr_plan(n, sample_rate)["n_autocorr"]
+        ac = np.zeros(nac) if full else None
+        tempo, lag, got = np.full(1, -1.0), np.full(1, -1, np.int64), C.c_int64()
+        self._check(self._L.sonar_tempo_autocorrelation(self._h, _ptr(pcm) if n else None, n, int(sample_rate),
+                                                        _ptr(tempo), _ptr(lag), _ptr(ac) if full and nac else None,
+                                                        C.byref(got), 0))
+        assert got.value == nac
+        return {"tempo": float(tempo[0]), "best_lag": int(lag[0]), "autocorr": ac}
+
+    def tempo_autocorrelation_device(self, pcm_ptr, n, sample_rate, tempo_ptr, best_lag_ptr=None, autocorr_ptr=None):
+        """tempo_autocorrelation on device memory (device_ptrs = 1): tempo (a double), best_lag (an int64)
+        and autocorr are device addresses -> n_autocorr."""
+        got = C.c_int64()
+        self._check(self._L.sonar_tempo_autocorrelation(self._h, pcm_ptr, int(n), int(sample_rate), tempo_ptr,
+                                                        best_lag_ptr, autocorr_ptr, C.byref(got), 1))
+        return got.value
+
+    def tempo(self, pcm, sample_rate, device_n=None):
+        """TempoEstimation.EstimateTempo, EstimateTempoAutocorrelation, EstimateTempoRange and
+        ClassifyTempoCategory (sonar_tempo) -> dict of the fields of sonar_tempo_result plus
+        category_name.  With device_n, pcm is a device address of that many doubles."""
+        r = TempoResult()
+        if device_n is None:
+            pcm = _f64(pcm)
+            self._check(self._L.sonar_tempo(self._h, _ptr(pcm) if pcm.size else None, len(pcm), int(sample_rate),
+                                            C.byref(r), 0))
+        else:
+            self._check(self._L.sonar_tempo(self._h, pcm, int(device_n), int(sample_rate), C.byref(r), 1))
+        out = {n: getattr(r, n) for n, _ in r._fields_}
+        out["category_name"] = tempo_category_name(r.category)
+        return out
 
     def key_frames(self, chroma, params=None, skip=()):
         """KeyEstimator.EstimateKey on every row of chroma (F x dim) (sonar_key_frames; params:
