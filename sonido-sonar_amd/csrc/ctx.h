@@ -41,7 +41,8 @@ struct PairTables {
   int* chunk_ks[2] = {};
   uint16_t* mel_src[2] = {};
   void* zeros = nullptr;    // 1024 zero samples of either PCM type (8 KB)
-  int J = 0, JS = 0, NMP = 0, n_mels = 0, n_mfcc = 0, max_src = 0;
+  int JS[2] = {};           // chunk_w row stride per precision (mfcc_pair_w_stride)
+  int J = 0, NMP = 0, n_mels = 0, n_mfcc = 0, max_src = 0;
 };
 
 struct IngestState;  // pinned slots + host pool of sonar_ingest_f64le (ingest_api.cpp)

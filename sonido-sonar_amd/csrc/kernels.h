@@ -104,7 +104,7 @@ struct MfccPairParams {
   const void* dct;      // [16][NMP + mfcc_pair_dct_pad] T: DCT-II rows with the lifter folded in
   const void* zeros;    // [1024] zero PCM samples (8 KB): the samples of frames past the signal
   int J;                // bins per chunk (<= 16)
-  int JS;               // chunk_w row stride = J | 1 (odd: conflict-free reads)
+  int JS;               // chunk_w row stride of this precision (mfcc_pair_w_stride: conflict-free reads)
   int max_src;          // most partial sums of one filter (<= 16)
   int NMP;              // n_mels padded to a multiple of 8 (<= 64)
   int n_mels, n_mfcc;   // n_mfcc <= 16
@@ -133,6 +133,19 @@ int mfcc_pair_rows();
 constexpr int mfcc_pair_pad_rows(int f64) { return f64 ? 1 : 2; }
 constexpr int mfcc_pair_dct_pad(int f64) { return f64 ? 2 : 4; }
 constexpr int kPairTw2Row = 9;
+// chunk_w row stride (complex per lane).  float32: the filterbank reads two bins' weights as one
+// ds_read_b128, so the stride is the smallest even JS >= J (J + 1 for odd J) with JS = 2 mod 4:
+// rows stay 16-byte aligned and the lane stride is an odd number of 16-byte units, which spreads
+// each 16-lane group of the read over all 64 banks.  float64 (16-byte reads of one bin): J | 1.
+#ifndef HL_W128
+#define HL_W128 1
+#endif
+constexpr int mfcc_pair_w128(int f64) { return HL_W128 && !f64; }
+constexpr int mfcc_pair_w_stride(int J, int f64) {
+  if (!mfcc_pair_w128(f64)) return J | 1;
+  const int m = J + (J & 1);
+  return (m & 3) == 2 ? m : m + 2;
+}
 bool fingerprint_supported(int W);
 int fp_batch_frames(int W, int f64, int spec);
 int fp_pre_rows(int W, int spec);

@@ -409,6 +409,14 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
 #define HL_SRC_REGS 1
 #endif
   constexpr bool SRC_REGS = HL_SRC_REGS && HC == 256 && MS > 0;
+  // LDS read forms of the float32 instances (DESIGN.md Kernel 1a "Read forms"): the T2 loads as
+  // single-address reads (the hop-256 instances; the runtime-hop ones spill with them and keep the
+  // compiler's loads), the filterbank weights two bins per 16-byte read
+#ifndef HL_T2_SINGLE
+#define HL_T2_SINGLE 1
+#endif
+  constexpr bool T2_SINGLE = HL_T2_SINGLE && sizeof(T) == 4 && HC == 256;
+  constexpr bool W128 = mfcc_pair_w128(sizeof(T) == 8);
   uint32_t srco[SRC_REGS ? MS : 1];
   if constexpr (SRC_REGS) {
 #pragma unroll
@@ -590,10 +598,40 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
       st2<T>(wb + t2b[t2_reg(1, c)] + 2 * L::CB * t2_pi(7 - c), v[8 + c].x, v[8 + c].y);
     }
     wave_lds_sync();
+    if constexpr (T2_SINGLE) {
+      // Sixteen ds_read_b64 from one address register (every offset fits the 16-bit immediate).  Left
+      // to the compiler, neighbouring loads merge into ds_read2st64_b64 / ds_read2_b64, which take 8
+      // LDS-array cycles for the 1 KiB that two single reads move in 4.  The outputs are 64-bit
+      // integers split by bit casts: a float2 output turns pass 3's adds into packed f32.  The block
+      // drains its own reads (the compiler does not count them); wave_lds_sync() follows anyway.
+      static_assert(7 * L::RS + 64 * L::CB < 65536, "T2 read offsets fit the DS immediate");
+      uint64_t q[16];
+      const uint32_t t2a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(wb + t2r);
+      asm volatile(
+          "ds_read_b64 %0, %16 offset:%c17\n\t"  "ds_read_b64 %1, %16 offset:%c18\n\t"
+          "ds_read_b64 %2, %16 offset:%c19\n\t"  "ds_read_b64 %3, %16 offset:%c20\n\t"
+          "ds_read_b64 %4, %16 offset:%c21\n\t"  "ds_read_b64 %5, %16 offset:%c22\n\t"
+          "ds_read_b64 %6, %16 offset:%c23\n\t"  "ds_read_b64 %7, %16 offset:%c24\n\t"
+          "ds_read_b64 %8, %16 offset:%c25\n\t"  "ds_read_b64 %9, %16 offset:%c26\n\t"
+          "ds_read_b64 %10, %16 offset:%c27\n\t" "ds_read_b64 %11, %16 offset:%c28\n\t"
+          "ds_read_b64 %12, %16 offset:%c29\n\t" "ds_read_b64 %13, %16 offset:%c30\n\t"
+          "ds_read_b64 %14, %16 offset:%c31\n\t" "ds_read_b64 %15, %16 offset:%c32\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3]), "=&v"(q[4]), "=&v"(q[5]), "=&v"(q[6]), "=&v"(q[7]),
+            "=&v"(q[8]), "=&v"(q[9]), "=&v"(q[10]), "=&v"(q[11]), "=&v"(q[12]), "=&v"(q[13]), "=&v"(q[14]), "=&v"(q[15])
+          : "v"(t2a),
+            "n"(0), "n"(L::RS), "n"(2 * L::RS), "n"(3 * L::RS), "n"(4 * L::RS), "n"(5 * L::RS), "n"(6 * L::RS), "n"(7 * L::RS),
+            "n"(64 * L::CB), "n"(64 * L::CB + L::RS), "n"(64 * L::CB + 2 * L::RS), "n"(64 * L::CB + 3 * L::RS),
+            "n"(64 * L::CB + 4 * L::RS), "n"(64 * L::CB + 5 * L::RS), "n"(64 * L::CB + 6 * L::RS), "n"(64 * L::CB + 7 * L::RS)
+          : "memory");
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-      v[j] = ld2<T>(wb + t2r + L::RS * j);
-      v[8 + j] = ld2<T>(wb + t2r + 64 * L::CB + L::RS * j);
+      for (int j = 0; j < 16; j++) v[j] = C{f_of((uint32_t)q[j]), f_of((uint32_t)(q[j] >> 32))};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        v[j] = ld2<T>(wb + t2r + L::RS * j);
+        v[8 + j] = ld2<T>(wb + t2r + 64 * L::CB + L::RS * j);
+      }
     }
     wave_lds_sync();
     if (HL_PHASE_PRIO) __builtin_amdgcn_s_setprio(1);
@@ -638,12 +676,30 @@ __global__ __launch_bounds__(sizeof(T) == 8 ? 512 : 768, 1) void mfcc_pair_kerne
       const int ib = 16 - (ks & 15);                          // first i past a pad pair
       const C* cw = s_cw + lane * p.JS;
       const int J = JT ? JT : p.J;
+      if constexpr (W128) {
+        // weights of bins (i, i + 1) as one 16-byte read: the row stride JS = 2 mod 4 keeps rows
+        // 16-byte aligned and the lane stride an odd number of 16-byte units (mfcc_pair_w_stride);
+        // an odd J's last bin is read singly, so no power row past the chunk is touched
+        auto bin = [&](int i, T wa, T wc) {                  // four FMAs per bin, ascending i
+          const C pp = ld2<T>(pr + L::PB * i + (i >= ib ? PR * L::PB : 0));
+          a0 += wa * pp.x; a1 += wa * pp.y;
+          c0 += wc * pp.x; c1 += wc * pp.y;
+        };
 #pragma unroll
-      for (int i = 0; i < J; i++) {
-        const C pp = ld2<T>(pr + L::PB * i + (i >= ib ? PR * L::PB : 0));
-        const C w = cw[i];
-        a0 += w.x * pp.x; a1 += w.x * pp.y;
-        c0 += w.y * pp.x; c1 += w.y * pp.y;
+        for (int i = 0; i + 1 < J; i += 2) {
+          const float4 w = *reinterpret_cast<const float4*>(cw + i);
+          bin(i, w.x, w.y);
+          bin(i + 1, w.z, w.w);
+        }
+        if (J & 1) bin(J - 1, cw[J - 1].x, cw[J - 1].y);
+      } else {
+#pragma unroll
+        for (int i = 0; i < J; i++) {
+          const C pp = ld2<T>(pr + L::PB * i + (i >= ib ? PR * L::PB : 0));
+          const C w = cw[i];
+          a0 += w.x * pp.x; a1 += w.x * pp.y;
+          c0 += w.y * pp.x; c1 += w.y * pp.y;
+        }
       }
       if constexpr (sizeof(T) == 8) {
         st2<T>(wb + L::PartOff + 16 * lane, a0, a1);

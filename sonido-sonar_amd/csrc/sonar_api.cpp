@@ -256,7 +256,6 @@ bool build_pair_tables(const sonar_fp_cfg* cfg, PairTables& t) {
     if (n <= 64) break;
   }
   const double scale = cfg->mfcc_input_power ? 1.0 / 16.0 : 0.25;   // |2X|^2 or |2X|^4 from the pair split
-  const int JS = J | 1;
   struct Chunk { int k0, seg; };
   std::vector<Chunk> chunks;
   for (size_t gi = 0; gi < segs.size(); gi++)
@@ -274,6 +273,8 @@ bool build_pair_tables(const sonar_fp_cfg* cfg, PairTables& t) {
                                      2, 2, 2, 2, 3, 3, 3, 3, 2, 2, 2, 2, 2, 2, 2, 2, 3, 3, 3, 3};
   for (int e = 0; e < 2; e++) {
     const int pad = sonar::mfcc_pair_pad_rows(e), ew = e ? 4 : 2;   // dwords per lane access
+    const int JS = sonar::mfcc_pair_w_stride(J, e);                 // weight row stride (zero-filled past J)
+    t.JS[e] = JS;
     auto group_of = [&](int l) { return e ? kB128Group[l] : l >> 5; };
     auto fb_conflicts = [&](const std::vector<int>& o) {
       int extra = 0;
@@ -365,7 +366,7 @@ bool build_pair_tables(const sonar_fp_cfg* cfg, PairTables& t) {
   t.window[1] = upload(win); t.tw1[1] = upload(tw1); t.tw2[1] = upload(tw2);
   t.dct[1] = upload(dct_rows(1));
   t.zeros = upload(std::vector<double>(1024, 0.0));
-  t.J = J; t.JS = JS; t.NMP = NMP; t.n_mels = mt.n_mels; t.n_mfcc = mt.n_mfcc;
+  t.J = J; t.NMP = NMP; t.n_mels = mt.n_mels; t.n_mfcc = mt.n_mfcc;
   t.ok = t.zeros != nullptr;
   for (int i = 0; i < 2; i++)
     t.ok = t.ok && t.window[i] && t.tw1[i] && t.tw2[i] && t.chunk_w[i] && t.dct[i] && t.chunk_ks[i] && t.mel_src[i];
@@ -575,10 +576,10 @@ void fill_pair_params(sonar_ctx* c, const PairTables& t, const sonar_fp_cfg* cfg
   q.f64 = e;
   q.window = t.window[e]; q.tw1 = t.tw1[e]; q.tw2 = t.tw2[e]; q.chunk_w = t.chunk_w[e]; q.dct = t.dct[e];
   q.chunk_ks = t.chunk_ks[e]; q.mel_src = t.mel_src[e]; q.zeros = t.zeros;
-  q.J = t.J; q.JS = t.JS; q.max_src = t.max_src; q.NMP = t.NMP; q.n_mels = t.n_mels; q.n_mfcc = t.n_mfcc;
+  q.J = t.J; q.JS = t.JS[e]; q.max_src = t.max_src; q.NMP = t.NMP; q.n_mels = t.n_mels; q.n_mfcc = t.n_mfcc;
   q.pow2 = cfg->mfcc_input_power != 0;
   auto al = [](int x) { return (x + 15) & ~15; };
-  q.lds_src = al(64 * t.JS * 2 * es);
+  q.lds_src = al(64 * t.JS[e] * 2 * es);
   q.lds_dct = q.lds_src + 64 * 16 * 2;
   q.lds_ctr = q.lds_dct + al(16 * (t.NMP + sonar::mfcc_pair_dct_pad(e)) * es);
   q.lds_tw2 = q.lds_ctr + 16;
