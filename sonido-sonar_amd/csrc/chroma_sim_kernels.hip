@@ -16,19 +16,13 @@
 
 #include "go_math.h"
 #include "kernels.h"
+#include "wave.h"
 
 namespace sonar {
 
 namespace {
 
 constexpr int T = CHROMA_DP_T;
-
-__device__ __forceinline__ double lane_bcast(double v, int j) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), j);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), j);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 
 // normalizeToProbability (distance.go:341-369) of v[0..dim) read through `at`, written to o
 template <typename F>
@@ -286,10 +280,10 @@ __global__ __launch_bounds__(1024) void chroma_ordered_sum_kernel(ChromaOrdArgs 
           const double x = vals[64 * k + lane];
 #pragma unroll
           for (int t = 0; t < 32; ++t)
-            if ((lo32 >> t) & 1) acc = acc + lane_bcast(x, t);
+            if ((lo32 >> t) & 1) acc = acc + readlane_f64(x, t);
 #pragma unroll
           for (int t = 0; t < 32; ++t)
-            if ((hi32 >> t) & 1) acc = acc + lane_bcast(x, 32 + t);
+            if ((hi32 >> t) & 1) acc = acc + readlane_f64(x, 32 + t);
         }
       }
       __syncthreads();

@@ -1,12 +1,6 @@
-// align_kernels.hip -- path B of the hot path on gfx950: normalized
-// cross-correlation and DTW, float64 like the Go reference.
+// dtw_kernels.hip -- path B of the hot path on gfx950: DTW, float64 like the Go reference
+// (the NCC of the same path is ncc_kernels.hip, the pair scorer pair_score_kernels.hip).
 //
-//  NCC  CrossCorrelation.Compute with NormalizedCrossCorrelation / TimeDomain
-//       (algorithms/stats/correlation.go:131-228, 373-409, 452-501) as configured by
-//       NewAlignmentAnalyzer (algorithms/stats/alignment.go:60-81).
-//       One thread per lag; every sum runs in Go's index order with unfused
-//       mul/add (__d*_rn), so correlations -- and therefore the peak lag -- are
-//       bit-identical to a sequential float64 evaluation.
 //  DTW  DTWAlignment.Align / fillCostMatrix / findPreviousStep / backtrack
 //       (algorithms/stats/dtw.go:55-217) with EuclideanDistanceFunc (distance.go:29-36);
 //       NewDTWAlignmentWithParams' step patterns (dtw.go:137-162) and Manhattan / Cosine / Pearson
@@ -24,6 +18,7 @@
 
 #include "go_math.h"
 #include "kernels.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -47,260 +42,6 @@ __device__ __forceinline__ double sqrt_normal(double x) {
 }
 constexpr double DTW_SQRT_MIN = 0x1p-767;   // below: the full sqrt() (its scaled range)
 }  // namespace
-
-// ---------------------------------------------------------------- NCC ----
-// stats[0..3] = mean_a, sd_a, mean_b, sd_b  (correlation.go:464-501, sequential sums)
-// Global z-score statistics (normalize :464-501): mean and population std of each input, every
-// sum sequential in Go's index order (bit-exact).  One wave per input: the wave loads 64
-// consecutive values per step (coalesced, the next step in flight), and every lane runs the
-// same sequential add chain over them through v_readlane broadcasts.
-__device__ __forceinline__ double lane_bcast(double v, int j) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), j);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), j);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-// a batched launch's job (blockIdx.y) into SGPRs
-template <class J>
-__device__ __forceinline__ J load_job(const J* p) {
-  static_assert(sizeof(J) % 4 == 0, "read as dwords");
-  J r;
-  const int* src = reinterpret_cast<const int*>(p);
-  int* dst = reinterpret_cast<int*>(&r);
-#pragma unroll
-  for (int k = 0; k < (int)(sizeof(J) / 4); ++k) dst[k] = __builtin_amdgcn_readfirstlane(src[k]);
-  return r;
-}
-
-// BJ (this and the two NCC kernels below): one pair per blockIdx.y, its arguments from jobs[]
-template <bool BJ = false>
-__global__ __launch_bounds__(64) void ncc_stats_kernel(const double* a, int64_t na, const double* b, int64_t nb,
-                                                       double* stats, const NccJob* jobs) {
-  SONAR_FEAT_PRIO();
-  if constexpr (BJ) {
-    const NccJob j = load_job(jobs + blockIdx.y);
-    a = j.a; na = j.na; b = j.b; nb = j.nb; stats = j.stats;
-  }
-  const int w = blockIdx.x;
-  const int lane = threadIdx.x;
-  const double* s = w ? b : a;
-  const int64_t n = w ? nb : na;
-  // full 64-value steps are unrolled (constant readlane indices, broadcasts issued ahead of the
-  // add chain); the tail runs the same chain with a runtime index
-  double mean = 0.0;
-  {
-    double cur = lane < n ? s[lane] : 0.0;
-    int64_t i = 0;
-    for (; i + 64 <= n; i += 64) {
-      const double nxt = i + 64 + lane < n ? s[i + 64 + lane] : 0.0;
-#pragma unroll
-      for (int j = 0; j < 64; j++) mean = __dadd_rn(mean, lane_bcast(cur, j));
-      cur = nxt;
-    }
-    for (int j = 0; j < (int)(n - i); j++) mean = __dadd_rn(mean, lane_bcast(cur, j));
-  }
-  mean = __ddiv_rn(mean, (double)n);
-  double var = 0.0;
-  {
-    double cur = lane < n ? __dsub_rn(s[lane], mean) : 0.0;
-    int64_t i = 0;
-    for (; i + 64 <= n; i += 64) {
-      const double nxt = i + 64 + lane < n ? __dsub_rn(s[i + 64 + lane], mean) : 0.0;
-#pragma unroll
-      for (int j = 0; j < 64; j++) {
-        const double d = lane_bcast(cur, j);
-        var = __dadd_rn(var, __dmul_rn(d, d));
-      }
-      cur = nxt;
-    }
-    for (int j = 0; j < (int)(n - i); j++) {
-      const double d = lane_bcast(cur, j);
-      var = __dadd_rn(var, __dmul_rn(d, d));
-    }
-  }
-  var = __ddiv_rn(var, (double)n);
-  if (lane == 0) {
-    stats[2 * w] = mean;
-    stats[2 * w + 1] = sqrt(var);
-  }
-}
-
-template <bool BJ = false>
-__global__ void ncc_norm_kernel(const double* a, int64_t na, const double* b, int64_t nb, const double* stats,
-                                double* xa, double* xb, const NccJob* jobs) {
-  SONAR_FEAT_PRIO();
-  if constexpr (BJ) {
-    const NccJob j = load_job(jobs + blockIdx.y);
-    a = j.a; na = j.na; b = j.b; nb = j.nb; stats = j.stats; xa = j.xa; xb = j.xb;
-  }
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < na) {
-    const double d = __dsub_rn(a[i], stats[0]);
-    xa[i] = stats[1] < 1e-10 ? d : __ddiv_rn(d, stats[1]);
-  }
-  if (i < nb) {
-    const double d = __dsub_rn(b[i], stats[2]);
-    xb[i] = stats[3] < 1e-10 ? d : __ddiv_rn(d, stats[3]);
-  }
-}
-
-// one lag per thread (normalizedCrossCorrelation, correlation.go:373-409), sums in Go's index
-// order (bit-exact).  A block owns 256 consecutive lags; their overlap windows start within 255
-// samples of each other (s1 = max(0, -lag), s2 = max(0, lag)), so each k-tile of both inputs is
-// staged once in LDS (coalesced) and every thread walks its own offsets there.
-constexpr int kNccTile = 1024;
-template <bool BJ = false>
-__global__ __launch_bounds__(256) void ncc_lag_kernel(const double* x, int64_t na, const double* y, int64_t nb,
-                                                      int64_t L, double* corr, const NccJob* jobs) {
-  SONAR_FEAT_PRIO();
-  __shared__ double xs[kNccTile + 256], ys[kNccTile + 256];
-  __shared__ int64_t ovmax_s;
-  if constexpr (BJ) {
-    const NccJob j = load_job(jobs + blockIdx.y);
-    x = j.xa; na = j.na; y = j.xb; nb = j.nb; L = j.L; corr = j.corr;
-  }
-  const int64_t nl = 2 * L + 1;
-  const int64_t idx0 = (int64_t)blockIdx.x * 256;
-  if (idx0 >= nl) return;
-  const int64_t idx = idx0 + threadIdx.x;
-  const bool active = idx < nl;
-  const int64_t lag = idx - L;
-  int64_t s1 = 0, e1 = 0, s2 = 0, e2 = 0;         // calculateOverlapRegion :421-449
-  if (lag >= 0) { s1 = 0; e1 = na; s2 = lag; e2 = nb; if (e1 > nb - lag) e1 = nb - lag; if (e2 > nb) e2 = nb; }
-  else { s1 = -lag; e1 = na; s2 = 0; e2 = nb; if (e1 > na) e1 = na; if (e2 > na + lag) e2 = na + lag; }
-  int64_t ov = (e1 - s1) < (e2 - s2) ? (e1 - s1) : (e2 - s2);
-  if (!active || ov < 0) ov = 0;
-  // window origins over the block's lags [idx0 - L, last - L]
-  const int64_t lastlag = (idx0 + 255 < nl ? idx0 + 255 : nl - 1) - L;
-  const int64_t x0 = lastlag < 0 ? -lastlag : 0;   // min s1
-  const int64_t y0 = idx0 - L > 0 ? idx0 - L : 0;   // min s2
-  if (threadIdx.x == 0) ovmax_s = 0;
-  __syncthreads();
-  atomicMax(reinterpret_cast<unsigned long long*>(&ovmax_s), (unsigned long long)ov);
-  __syncthreads();
-  const int64_t ovmax = ovmax_s;
-  const int ox = (int)(s1 - x0), oy = (int)(s2 - y0);   // 0..255 for active lags
-  double sm = 0.0, q1 = 0.0, q2 = 0.0;
-  for (int64_t k0 = 0; k0 < ovmax; k0 += kNccTile) {
-    for (int j = threadIdx.x; j < kNccTile + 256; j += 256) {
-      const int64_t gx = x0 + k0 + j, gy = y0 + k0 + j;
-      xs[j] = gx < na ? x[gx] : 0.0;
-      ys[j] = gy < nb ? y[gy] : 0.0;
-    }
-    __syncthreads();
-    int kend = ov - k0 < kNccTile ? (int)(ov - k0) : kNccTile;
-    if (kend < 0) kend = 0;
-    const double* px = xs + ox;
-    const double* py = ys + oy;
-    int k = 0;
-    for (; k + 4 <= kend; k += 4) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const double c1 = px[k + j], c2 = py[k + j];
-        sm = __dadd_rn(sm, __dmul_rn(c1, c2));
-        q1 = __dadd_rn(q1, __dmul_rn(c1, c1));
-        q2 = __dadd_rn(q2, __dmul_rn(c2, c2));
-      }
-    }
-    for (; k < kend; k++) {
-      const double c1 = px[k], c2 = py[k];
-      sm = __dadd_rn(sm, __dmul_rn(c1, c2));
-      q1 = __dadd_rn(q1, __dmul_rn(c1, c1));
-      q2 = __dadd_rn(q2, __dmul_rn(c2, c2));
-    }
-    __syncthreads();
-  }
-  if (!active) return;
-  double c = 0.0;
-  if (ov > 0) {
-    const double dn = sqrt(__dmul_rn(q1, q2));
-    c = dn < 1e-10 ? 0.0 : __ddiv_rn(sm, dn);
-  }
-  corr[idx] = c;
-}
-
-int launch_ncc(const double* a, int64_t na, const double* b, int64_t nb, int64_t L, double* xa, double* xb,
-               double* stats, double* corr, hipStream_t s) {
-  const NccJob* none = nullptr;
-  hipLaunchKernelGGL((ncc_stats_kernel<false>), dim3(2), dim3(64), 0, s, a, na, b, nb, stats, none);
-  const int64_t nmax = na > nb ? na : nb;
-  hipLaunchKernelGGL((ncc_norm_kernel<false>), dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, s, a, na, b, nb, stats, xa,
-                     xb, none);
-  const int64_t nl = 2 * L + 1;
-  hipLaunchKernelGGL((ncc_lag_kernel<false>), dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, xa, na, xb, nb, L, corr,
-                     none);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-// launch_ncc's kernels one by one (sonar_xcorr_params: the same z-score under every type and method)
-int launch_ncc_stats(const double* a, int64_t na, const double* b, int64_t nb, double* stats, hipStream_t s) {
-  const NccJob* none = nullptr;
-  hipLaunchKernelGGL((ncc_stats_kernel<false>), dim3(2), dim3(64), 0, s, a, na, b, nb, stats, none);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-int launch_ncc_zscore(const double* a, int64_t na, const double* b, int64_t nb, double* xa, double* xb, double* stats,
-                      hipStream_t s) {
-  const NccJob* none = nullptr;
-  hipLaunchKernelGGL((ncc_stats_kernel<false>), dim3(2), dim3(64), 0, s, a, na, b, nb, stats, none);
-  const int64_t nmax = na > nb ? na : nb;
-  hipLaunchKernelGGL((ncc_norm_kernel<false>), dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, s, a, na, b, nb, stats, xa,
-                     xb, none);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-int launch_ncc_lags(const double* xa, int64_t na, const double* xb, int64_t nb, int64_t L, double* corr, hipStream_t s) {
-  const NccJob* none = nullptr;
-  const int64_t nl = 2 * L + 1;
-  hipLaunchKernelGGL((ncc_lag_kernel<false>), dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, xa, na, xb, nb, L, corr,
-                     none);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-// launch_ncc over many pairs in three launches (blockIdx.y = pair); the same kernels, arithmetic
-// and order per pair, so the same bits
-int launch_ncc_batch(const NccJob* hjobs, const NccJob* djobs, int nj, hipStream_t s) {
-  if (nj <= 0) return 0;
-  if (nj > 65535) return -1;
-  int64_t nmax = 1, nlmax = 1;
-  for (int k = 0; k < nj; ++k) {
-    nmax = std::max(nmax, std::max(hjobs[k].na, hjobs[k].nb));
-    nlmax = std::max(nlmax, 2 * hjobs[k].L + 1);
-  }
-  hipLaunchKernelGGL((ncc_stats_kernel<true>), dim3(2, (unsigned)nj), dim3(64), 0, s, nullptr, 0, nullptr, 0, nullptr,
-                     djobs);
-  hipLaunchKernelGGL((ncc_norm_kernel<true>), dim3((unsigned)((nmax + 255) / 256), (unsigned)nj), dim3(256), 0, s,
-                     nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, djobs);
-  hipLaunchKernelGGL((ncc_lag_kernel<true>), dim3((unsigned)((nlmax + 255) / 256), (unsigned)nj), dim3(256), 0, s,
-                     nullptr, 0, nullptr, 0, 0, nullptr, djobs);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-// AlignmentAnalyzer.addNoise (alignment.go:737-749): out[i][j] = q + (sin(i*j+i+j) * level) * q
-__global__ void perturb_kernel(const double* q, int64_t nq, int dim, double level, double* out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= nq * dim) return;
-  const int64_t i = idx / dim, j = idx - i * dim;
-  const double v = q[idx];
-  out[idx] = __dadd_rn(v, __dmul_rn(__dmul_rn(sin((double)(i * j + i + j)), level), v));
-}
-// flatten2DFeatures (:363-378): the first component of every frame
-__global__ void first_column_kernel(const double* x, int64_t n, int dim, double* out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = x[i * dim];
-}
-int launch_perturb(const double* q, int64_t nq, int dim, double level, double* out, hipStream_t s) {
-  const int64_t n = nq * dim;
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(perturb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, nq, dim, level, out);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-int launch_first_column(const double* x, int64_t n, int dim, double* out, hipStream_t s) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(first_column_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, dim, out);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
 
 // ---------------------------------------------------------------- DTW ----
 // Forward sweep (fillCostMatrix + applyStepPattern "symmetric2", dtw.go:106-135,138-143)
@@ -373,8 +114,6 @@ constexpr uint64_t DTW_REFRESH_TICKS = 100000ull;
 #define DTW_SPIN_SLEEP 4                            // s_sleep between LDS counter polls (A/B 0,1,4,8,16: 4-8 best)
 #endif
 
-static_assert(sizeof(DtwArgs) % 4 == 0, "read as dwords");
-
 // Many independent DTWs in one band-kernel launch: a block's ticket t runs over every DTW's bands
 // in order (DTW k owns tickets [start[k], start[k+1])), so each DTW's bands still start in band
 // order, and a DTW's first band starts as soon as the previous DTW's last band holds a slot.
@@ -387,20 +126,10 @@ struct DtwBatch {
                      // has the smaller ticket; null: DTW-major through `start`
 };
 
-namespace {
-
-// a DtwArgs at a wave-uniform address into SGPRs (every field read through readfirstlane).  The
-// compiler cannot tell that its pointers address global memory: accesses through them that matter
-// go through DTW_GLOBAL / g_load_agent / g_store_agent (global_* instead of flat_*)
-__device__ __forceinline__ DtwArgs load_args_uniform(const DtwArgs* p) {
-  DtwArgs r;
-  const int* src = reinterpret_cast<const int*>(p);
-  int* dst = reinterpret_cast<int*>(&r);
-#pragma unroll
-  for (int k = 0; k < (int)(sizeof(DtwArgs) / 4); ++k) dst[k] = __builtin_amdgcn_readfirstlane(src[k]);
-  return r;
-}
-}  // namespace
+// The batched kernels read their DtwArgs at a wave-uniform address into SGPRs with load_job
+// (wave.h: every field through readfirstlane).  The compiler cannot tell that its pointers address
+// global memory: accesses through them that matter go through DTW_GLOBAL / g_load_agent /
+// g_store_agent (global_* instead of flat_*)
 
 namespace {
 __device__ __forceinline__ double shr1(double v, double lane0) {
@@ -421,10 +150,6 @@ __device__ __forceinline__ double vmin_f64(double x, double y) {
   double r;
   asm volatile("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
   return r;
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int2 a = __builtin_bit_cast(int2, v);
-  return __builtin_bit_cast(double, make_int2(__builtin_amdgcn_readlane(a.x, l), __builtin_amdgcn_readlane(a.y, l)));
 }
 }  // namespace
 
@@ -787,7 +512,7 @@ void dtw_band_kernel(DtwArgs a_in, DtwBatch bt) {
   }
   __syncthreads();
   const int64_t b = shb;
-  const DtwArgs a = BATCH ? load_args_uniform(bt.args + __builtin_amdgcn_readfirstlane(shk)) : a_in;
+  const DtwArgs a = BATCH ? load_job(bt.args + __builtin_amdgcn_readfirstlane(shk)) : a_in;
   if (b >= a.nb) return;
   const int64_t nq = a.nq, nr = a.nr, S = a.S, S2 = (a.S + 1) >> 1;
   const int dim = D > 0 ? D : a.dim;
@@ -1505,7 +1230,7 @@ __global__ __launch_bounds__(64) void dtw_walk_kernel(const uint32_t* Dn, int64_
 
 // one block per DTW of a batch (the walks are independent)
 __global__ __launch_bounds__(64) void dtw_walk_batch_kernel(const DtwArgs* args) {
-  const DtwArgs a = load_args_uniform(args + blockIdx.x);
+  const DtwArgs a = load_job(args + blockIdx.x);
   dtw_walk_body(a.Dn, a.nq, a.nr, a.SW, a.codes, a.plen);
 }
 
@@ -1561,7 +1286,7 @@ __device__ __forceinline__ void dtw_xm_block(const uint32_t (&cw)[4], int t0, in
 
 template <bool BATCH>
 __global__ __launch_bounds__(64) void dtw_exit_map_kernel(DtwArgs a_in, const DtwArgs* args) {
-  const DtwArgs a = BATCH ? load_args_uniform(args + blockIdx.z) : a_in;
+  const DtwArgs a = BATCH ? load_job(args + blockIdx.z) : a_in;
   const int64_t b = blockIdx.y, k = blockIdx.x;
   const int64_t nq = a.nq, nr = a.nr, nb = a.nb, SW = a.SW, nseg = dtw_nseg(nr);
   if (b >= nb || k >= nseg) return;
@@ -1606,7 +1331,7 @@ __global__ __launch_bounds__(64) void dtw_exit_map_kernel(DtwArgs a_in, const Dt
 
 template <bool BATCH>
 __global__ __launch_bounds__(64) void dtw_walk_chain_kernel(DtwArgs a_in, const DtwArgs* args) {
-  const DtwArgs a = BATCH ? load_args_uniform(args + blockIdx.x) : a_in;
+  const DtwArgs a = BATCH ? load_job(args + blockIdx.x) : a_in;
   if (threadIdx.x != 0) return;
   const int64_t nb = a.nb, nr64 = dtw_nr64(a.nr), nseg = dtw_nseg(a.nr);
   const int32_t* X = dtw_xmap(a.Dn, nb, a.SW);
@@ -1627,7 +1352,7 @@ __global__ __launch_bounds__(64) void dtw_walk_chain_kernel(DtwArgs a_in, const 
 
 template <bool EMIT, bool BATCH>
 __global__ __launch_bounds__(64) void dtw_walk_band_kernel(DtwArgs a_in, const DtwArgs* args) {
-  const DtwArgs a = BATCH ? load_args_uniform(args + blockIdx.y) : a_in;
+  const DtwArgs a = BATCH ? load_job(args + blockIdx.y) : a_in;
   const int64_t nb = a.nb;
   const int bnd = (int)blockIdx.x;
   if (bnd >= nb) return;
@@ -1693,7 +1418,7 @@ __global__ __launch_bounds__(64) void dtw_walk_band_kernel(DtwArgs a_in, const D
 template <bool BATCH>
 __global__ __launch_bounds__(1024) void dtw_walk_scan_kernel(DtwArgs a_in, const DtwArgs* args) {
   __shared__ int64_t wsum[16];
-  const DtwArgs a = BATCH ? load_args_uniform(args + blockIdx.x) : a_in;
+  const DtwArgs a = BATCH ? load_job(args + blockIdx.x) : a_in;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, NT = (int)blockDim.x, NWV = NT >> 6;
   const int64_t nb = a.nb;
   int32_t* meta = dtw_walk_meta(a.Dn, nb, a.SW, a.nr);
@@ -1747,7 +1472,7 @@ __global__ __launch_bounds__(1024) void dtw_path_scan_kernel(const uint32_t* cod
   __shared__ int64_t wsum[2][16];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, NT = (int)blockDim.x;   // 64..1024 (see walk scan)
   if constexpr (BATCH) {
-    const DtwArgs a = load_args_uniform(args + blockIdx.x);
+    const DtwArgs a = load_job(args + blockIdx.x);
     codes = a.codes; P = *a.plen; nq = a.nq; nr = a.nr; wstart = a.wstart;
     if (t == 0 && a.Cn) *a.cnm = cn_at(a.Cn, a.S, nq, nr);   // (CK mode: the tile pass writes it)
   }
@@ -1793,7 +1518,7 @@ __global__ __launch_bounds__(256) void dtw_path_points_kernel(const uint32_t* co
                                                               const double* Cn, int64_t S, int32_t* pq, int32_t* pr,
                                                               double* pc, const DtwArgs* args) {
   if constexpr (BATCH) {
-    const DtwArgs a = load_args_uniform(args + blockIdx.y);
+    const DtwArgs a = load_job(args + blockIdx.y);
     codes = a.codes; wstart = a.wstart; P = *a.plen; Cn = a.Cn; S = a.S; pq = a.pq; pr = a.pr; pc = a.pc;
   }
   const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1833,7 +1558,7 @@ __global__ __launch_bounds__(256) void dtw_path_points_kernel(const uint32_t* co
 //    (127 steps, lane = row, distances inline), each path point's cost taken at its own step.
 template <bool BATCH>
 __global__ __launch_bounds__(256) void dtw_path_runs_kernel(DtwArgs a_in, const DtwArgs* args) {
-  const DtwArgs a = BATCH ? load_args_uniform(args + blockIdx.y) : a_in;
+  const DtwArgs a = BATCH ? load_job(args + blockIdx.y) : a_in;
   const int64_t P = *a.plen;
   const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= P) return;
@@ -1862,7 +1587,7 @@ __device__ __forceinline__ void dtw_path_tile_body(DtwArgs a_in, const DtwArgs* 
   __shared__ __attribute__((aligned(16))) double Rt[D > 0 ? 64 * D : 2];   // D > 0: the tile's reference rows
   __shared__ double top[66];                         // C[64bi][jb + c], c = 0 .. 64
   __shared__ int rlo[64], rhi[64], rf[64];           // the run's points in row li: columns, first index
-  const DtwArgs a = BATCH ? load_args_uniform(args + blockIdx.y) : a_in;
+  const DtwArgs a = BATCH ? load_job(args + blockIdx.y) : a_in;
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= a.runs[0]) return;
   const int64_t P = *a.plen, nq = a.nq, nr = a.nr;
@@ -2023,7 +1748,7 @@ __global__ void nonfinite_kernel(const double* x, int64_t n, int32_t* flag) {
 // path-tile run counters (what a hipMemsetD32Async and a hipMemsetAsync per batch did before).
 // Same stream, earlier kernel: the stores are visible to the band kernel's sc1 polls.
 __global__ void nonfinite_batch_kernel(const DtwArgs* args) {
-  const DtwArgs a = load_args_uniform(args + blockIdx.y);
+  const DtwArgs a = load_job(args + blockIdx.y);
   const int64_t nqe = a.nq * a.dim, n = nqe + a.nr * a.dim;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride)
@@ -2252,219 +1977,6 @@ int launch_nonfinite_batch(const DtwArgs* dargs, int n, int64_t max_elems, hipSt
   int64_t blocks = (max_elems + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(nonfinite_batch_kernel, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, s, dargs);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-// sonar_align_pairs' scorer reductions on the device (alignment.go:380-643, correlation.go:526-667):
-// one wave per pair over its warping path and energy correlation -- host::path_sums and
-// host::corr_sums, bit for bit -- so a batch copies back ~150 bytes per pair instead of its path
-// (16 B per point) and correlation, and its host thread only combines scalars.  Counts, extrema
-// and the peak index (the first index of the largest |corr|, as Go's strict > scan) are order-free;
-// the float sums keep Go's sequential order: 64 terms are formed at once (a smoothed cost is Go's
-// window sum, a deviation is squared before it is added, as Go does) and then added one by one in
-// index order (seq_add below).
-namespace {
-__device__ __forceinline__ int64_t wave_isum(int64_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// the largest a over the wave (ties: the smallest index); a = -1 for "none"
-__device__ __forceinline__ void wave_argmax(double& a, int64_t& i) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ao = __shfl_xor(a, o, 64);
-    const int64_t io = __shfl_xor(i, o, 64);
-    if (ao > a || (ao == a && io < i)) { a = ao; i = io; }
-  }
-}
-}  // namespace
-
-// Sequential sums of 64 terms at a time (acc += v[lane 0], += v[lane 1], ... in lane order, for
-// NC independent sums at once).  Round 6: the terms go through LDS and every lane runs the add chain
-// on broadcast reads, so a term costs one dependent v_add_f64 (the reads are independent and issue
-// ahead) instead of two v_readlane + the SGPR hazard + the add (3.2 -> 2.0 ms per launch).
-template <int NC>
-__device__ __forceinline__ void seq_add(double (&acc)[NC], const double (&v)[NC], int cnt, double* buf) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) buf[64 * c + lane] = v[c];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  // 32 terms per sum into registers with every read issued up front, then the adds in order
-  for (int k0 = 0; k0 < cnt; k0 += 32) {
-    double r[NC][32];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int q = 0; q < 32; q += 2) {
-        const double2 v2 = *reinterpret_cast<const double2*>(&buf[64 * c + k0 + q]);
-        r[c][q] = v2.x; r[c][q + 1] = v2.y;
-      }
-    if (k0 + 32 <= cnt) {
-#pragma unroll
-      for (int q = 0; q < 32; ++q)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) acc[c] += r[c][q];
-    } else {
-#pragma unroll
-      for (int q = 0; q < 32; ++q)
-        if (k0 + q < cnt) {
-#pragma unroll
-          for (int c = 0; c < NC; ++c) acc[c] += r[c][q];
-        }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // the next block's stores after every read
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-constexpr int SU = 4;   // 64-term steps whose terms are formed before their adds (loads in flight)
-__global__ __launch_bounds__(64) void pair_score_kernel(const ScoreJob* jobs) {
-  const ScoreJob j = jobs[blockIdx.x];
-  const int lane = threadIdx.x;
-  __shared__ __attribute__((aligned(16))) double sbuf[2 * 64];
-  // ---- warping path
-  const int64_t P = *j.plen;
-  host::PathSums ps;
-  ps.P = P;
-  if (P > 0) {
-    int64_t off = 0, dg = 0, ch = 0;
-    const int64_t w = max((int64_t)2, min((int64_t)5, P / 4)), h = w / 2;
-    auto smooth = [&](int64_t i) {                  // calculateCostConsistency's window mean
-      double t = 0.0;
-      const int64_t lo = max((int64_t)0, i - h), hi = min(P - 1, i + h);
-      for (int64_t q = lo; q <= hi; ++q) t += j.pc[q];
-      return t / (double)(hi - lo + 1);
-    };
-    double sc = 0.0, ss = 0.0;                       // Go's sequential sums (wave-uniform)
-    // SU steps of 64 terms are formed first (their path loads all in flight at once), then added
-    for (int64_t b0 = 0; b0 < P; b0 += 64 * SU) {
-      double cu[SU], mu[SU];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int64_t i = b0 + 64 * u + lane;
-        double c = 0.0, m = 0.0;
-        if (i < P) {
-          off += j.pr[i] - j.pq[i];
-          c = j.pc[i];
-          if (P > 1) m = smooth(i);
-          if (i >= 1) {
-            const int d0 = j.pq[i] - j.pq[i - 1], d1 = j.pr[i] - j.pr[i - 1];
-            if (d0 > 0 && d1 > 0) dg++;
-            if (i >= 2 && (d0 != j.pq[i - 1] - j.pq[i - 2] || d1 != j.pr[i - 1] - j.pr[i - 2])) ch++;
-          }
-        }
-        cu[u] = c; mu[u] = m;
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int64_t b = b0 + 64 * u;
-        if (b < P) {
-          const int cnt = (int)min((int64_t)64, P - b);
-          double acc[2] = {sc, ss};
-          const double v[2] = {cu[u], mu[u]};
-          seq_add<2>(acc, v, cnt, sbuf);
-          sc = acc[0]; ss = acc[1];
-        }
-      }
-    }
-    ps.offset_sum = wave_isum(off);
-    ps.diag_steps = wave_isum(dg);
-    ps.changes = wave_isum(ch);
-    ps.sum_cost = sc;
-    ps.p0q = j.pq[0]; ps.p0r = j.pr[0]; ps.p1q = j.pq[P - 1]; ps.p1r = j.pr[P - 1];
-    if (P > 1) {
-      ps.sum_smooth = ss;
-      const double mean = ss / (double)P;
-      double vv = 0.0;
-      for (int64_t b0 = 0; b0 < P; b0 += 64 * SU) {
-        double du[SU];
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int64_t i = b0 + 64 * u + lane;
-          double d2 = 0.0;
-          if (i < P) { const double d = smooth(i) - mean; d2 = d * d; }
-          du[u] = d2;
-        }
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int64_t b = b0 + 64 * u;
-          if (b < P) {
-            const int cnt = (int)min((int64_t)64, P - b);
-            double acc[1] = {vv};
-            const double v[1] = {du[u]};
-            seq_add<1>(acc, v, cnt, sbuf);
-            vv = acc[0];
-          }
-        }
-      }
-      ps.var_smooth = vv;
-    }
-  }
-  if (lane == 0) *j.path = ps;
-  // ---- energy correlation
-  if (!j.corr) return;
-  const int64_t nl = j.nl;
-  host::CorrSums cs;
-  cs.num_lags = nl;
-  if (nl > 0) {
-    // findPeak: Go keeps corr[0] unless a strictly larger |corr| follows (a NaN corr[0] is kept)
-    double a = -1.0;
-    int64_t pi = nl;
-    for (int64_t i = lane; i < nl; i += 64) {
-      const double v = fabs(j.corr[i]);
-      if (v > a) { a = v; pi = i; }                  // NaN never wins
-    }
-    wave_argmax(a, pi);
-    const double c0 = j.corr[0];
-    if (isnan(c0) || !(a > fabs(c0))) pi = 0;        // nothing strictly larger than |corr[0]|
-    cs.peak_index = pi;
-    cs.peak = j.corr[pi];
-    double ns = 0.0, sa = -1.0, ms = 0.0;
-    int64_t nc = 0, si = nl;
-    for (int64_t b0 = 0; b0 < nl; b0 += 64 * SU) {
-      double qu[SU];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int64_t i = b0 + 64 * u + lane;
-        double sq = 0.0;                             // terms outside the mask add an exact +0
-        if (i < nl) {
-          const double c = j.corr[i], v = fabs(c);
-          const int64_t d = i > pi ? i - pi : pi - i;
-          if (d > 5) { sq = c * c; nc++; }
-          if (i != pi && v > sa) { sa = v; si = i; }
-          if (d > 10 && v > ms) ms = v;
-        }
-        qu[u] = sq;
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int64_t b = b0 + 64 * u;
-        if (b < nl) {
-          const int cnt = (int)min((int64_t)64, nl - b);
-          double acc[1] = {ns};
-          const double v[1] = {qu[u]};
-          seq_add<1>(acc, v, cnt, sbuf);
-          ns = acc[0];
-        }
-      }
-    }
-    cs.noise_sum = ns;
-    cs.noise_count = wave_isum(nc);
-    wave_argmax(sa, si);
-    cs.second_peak = (si < nl && sa > 0.0) ? j.corr[si] : 0.0;   // Go starts from 0 with a strict >
-    int64_t mi = 0;
-    wave_argmax(ms, mi);                             // a max of non-negative values
-    cs.max_sidelobe = ms;
-    if (nl >= 3 && pi > 0 && pi < nl - 1) cs.sharpness = -(j.corr[pi + 1] - 2 * j.corr[pi] + j.corr[pi - 1]);
-  }
-  if (lane == 0) *j.corr_out = cs;
-}
-
-int launch_pair_scores(const ScoreJob* djobs, int n, hipStream_t s) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(pair_score_kernel, dim3((unsigned)n), dim3(64), 0, s, djobs);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -29,6 +29,7 @@
 //    are staged in LDS and written with coalesced stores.
 #include "kernels.h"
 #include "twiddles.h"
+#include "wave.h"
 
 namespace sonar {
 
@@ -79,13 +80,7 @@ __device__ __forceinline__ void dft_reg(T (&re)[N], T (&im)[N]) {
   }
 }
 
-// orders LDS traffic of one wave (cross-lane exchange through LDS): fence + wave barrier pin
-// the DS ops in place; the explicit lgkmcnt(0) retires them before the next phase (defensive).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
+// wave_lds_sync (wave.h) orders the LDS traffic of one wave's cross-lane exchanges through LDS.
 
 template <typename T>
 __device__ __forceinline__ T load_pcm(const void* pcm, int pcm_f64, int64_t i) {
@@ -520,14 +515,11 @@ void fp_wave_kernel(FpParams p) {
           if (has_prev) { const T d = m - prev[k]; if (d > (T)0) s_fx += d * d; }
         }
       }
-      auto red = [&](T v) { for (int o = NG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; };
-      auto redd = [&](double v) { for (int o = NG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; };
-      auto redi = [&](int v) { for (int o = NG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; };
-      auto redmax = [&](T v) { for (int o = NG / 2; o > 0; o >>= 1) { const T u = __shfl_xor(v, o, 64); v = u > v ? u : v; } return v; };
-      const T S_m = red(s_m), S_fm = red(s_fm), S_m2 = red(s_m2), MX = redmax(mx), S_ln = red(s_ln);
+      auto red = [](auto v) { return wave_sum<decltype(v), NG>(v); };        // over the frame's NG lanes
+      const T S_m = red(s_m), S_fm = red(s_fm), S_m2 = red(s_m2), MX = wave_max<T, NG>(mx), S_ln = red(s_ln);
       const T S_lo = red(s_lo), S_hi = red(s_hi), S_fx = red(s_fx);
-      const double SX = redd(sx), SY = redd(sy), SXY = redd(sxy), SXX = redd(sxx);
-      const int N_ln = redi(n_ln), N_sl = redi(n_sl);
+      const double SX = red(sx), SY = red(sy), SXY = red(sxy), SXX = red(sxx);
+      const int N_ln = red(n_ln), N_sl = red(n_sl);
       const T cen = (S_m == (T)0) ? (T)0 : S_fm / S_m;                       // spectral_centroid.go:18-41
       T s_bw = 0;                                                            // spectral_bandwidth.go:22-47
       if (act) {
@@ -618,26 +610,6 @@ void fp_wave_kernel(FpParams p) {
 // spectral_rolloff.go:29-49, spectral_bandwidth.go:22-47, spectral_flatness.go:31-73,
 // spectral_crest.go:18-38, spectral_slope.go:23-63, spectral_flux.go:299-318.
 namespace {
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
-  return v;
-}
 // body(j) over the lane's chunk j < nk, fully unrolled when CHM > 0; body returns true to stop
 template <int CHM, typename B>
 __device__ __forceinline__ void chunk_for(int nk, B body) {
@@ -732,10 +704,10 @@ __global__ __launch_bounds__(256) void spec_rows_kernel(SpecParams p) {
     const double S_m = wave_sum(s_m), S_fm = wave_sum(s_fm), S_m2 = wave_sum(s_m2), MX = wave_max(mx);
     const double S_ln = wave_sum(s_ln), S_lo = wave_sum(s_lo), S_hi = wave_sum(s_hi);
     const double S_fx = has_prev ? wave_sum(s_fx) : 0.0;
-    const int N_ln = wave_sum_i(n_ln);
+    const int N_ln = wave_sum(n_ln);
     double SX = 0, SY = 0, SXY = 0, SXX = 0;
     int N_sl = 0;
-    if (slope_on) { SX = wave_sum(sx); SY = wave_sum(sy); SXY = wave_sum(sxy); SXX = wave_sum(sxx); N_sl = wave_sum_i(n_sl); }
+    if (slope_on) { SX = wave_sum(sx); SY = wave_sum(sy); SXY = wave_sum(sxy); SXX = wave_sum(sxx); N_sl = wave_sum(n_sl); }
     const double cen = (S_m == 0.0) ? 0.0 : S_fm / S_m;
     double s_bw = 0;
     chunk_for<CHM>(nk, [&](int j) {
@@ -771,10 +743,10 @@ __global__ __launch_bounds__(256) void spec_rows_kernel(SpecParams p) {
         });
       }
       bool owner = ridx < (1 << 30);
-      ridx = wave_min_i(ridx);
+      ridx = wave_min(ridx);
       owner = owner && ridx >= k0 && ridx < k1;
       int unsure = (owner && !(margin > delta)) ? 1 : 0;
-      unsure = wave_sum_i(unsure);
+      unsure = wave_sum(unsure);
       if (tot != 0.0 && ridx >= K) unsure = 1;                  // rounding kept every cum below target
       roll_zero = (tot == 0.0);
       if (unsure) {                                             // wave-uniform: Go's chains on lane 0

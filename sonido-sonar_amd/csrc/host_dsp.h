@@ -53,7 +53,7 @@ struct NccMetrics {
 // The O(lags) part of those metrics: findPeak's index and value, calculateSNR's noise sum and count
 // (|i - peak| > 5), findSecondPeak's value, calculatePeakToSidelobe's sidelobe maximum (|i - peak|
 // > 10) and calculateSharpness's second difference (0 at the ends).  corr_sums runs Go's loops; the
-// batched pair path computes the same on the device (pair_score_kernel, align_kernels.hip), every
+// batched pair path computes the same on the device (pair_score_kernel, pair_score_kernels.hip), every
 // sum in Go's index order with masked terms added as exact zeros, so the two are bit-identical
 // (test_device_scorer_equals_host_scorer).  Plain data, shared with the kernels.
 struct CorrSums {

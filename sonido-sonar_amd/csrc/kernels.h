@@ -188,7 +188,7 @@ int launch_stats(const double* y, int64_t n, double* part, int blocks, hipStream
 int launch_tilt(const double* y, int64_t n, int64_t frames, double* tilt, hipStream_t s);
 // PCM ingest: f64 -> f32 (RNE); both pointers 16-B aligned (misc_kernels.hip)
 int launch_f64_to_f32(const double* in, float* out, int64_t n, hipStream_t s);
-// NCC (align_kernels.hip)
+// NCC (ncc_kernels.hip)
 // One signal of a batched music-feature launch (launch_music_features_batch): its PCM, the
 // pre-emphasised output, the DC chunk scratch (T chunks), energy (Fe frames) and chroma (F frames)
 struct MfJob {
@@ -265,10 +265,10 @@ struct CqtArgs {
   double* chroma;         // F x 12
 };
 int launch_chroma_cqt(const CqtArgs& a, hipStream_t s);
-// AlignmentAnalyzer.addNoise and flatten2DFeatures (align_kernels.hip)
+// AlignmentAnalyzer.addNoise and flatten2DFeatures (ncc_kernels.hip)
 int launch_perturb(const double* q, int64_t nq, int dim, double level, double* out, hipStream_t s);
 int launch_first_column(const double* x, int64_t n, int dim, double* out, hipStream_t s);
-// DTW (dtw.go:55-217).  Band-pipelined persistent kernel; see align_kernels.hip.
+// DTW (dtw.go:55-217).  Band-pipelined persistent kernel; see dtw_kernels.hip.
 struct DtwGeom {
   int64_t nq, nr;   // sequence lengths
   int64_t nb;       // 64-row bands = ceil(nq / 64)

@@ -16,6 +16,7 @@
 //     with the serial scans' exact outcome; validate / spacing / VTL / quality (:300-411) lane 0
 #include "../../include/sonar_gpu.h"
 #include "kernels.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -39,7 +40,7 @@ __device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : 
 
 template <int NT>
 __device__ double block_sum(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum(v);
   const int w = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[w] = v;

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "wave.h"
 
 namespace sonar {
 
@@ -216,16 +217,7 @@ __device__ __forceinline__ void swap8x4(double (&a)[4], double (&b)[4], uint64_t
   }
 }
 
-// Phase boundary of the wave-private LDS exchanges: the fence and wave barrier keep the
-// compiler from moving DS ops across it; the explicit lgkmcnt(0) retires every DS op of the
-// phase before the next phase reads other lanes' words (defensive; costs < 2 % here).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#ifndef SONAR_NO_LGKM_SYNC
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-  __builtin_amdgcn_wave_barrier();
-}
+// wave_lds_sync (wave.h) is the phase boundary of the wave-private LDS exchanges below.
 
 // T2 buffer, "b0-major": the 8-vector (over b0) of residue r is 8 complex RS apart, element b0 at
 // complex index RS b0 + u, u = t2_col(L) for slot A of reader lane L and t2_col(L) + 64 for slot B.

@@ -15,6 +15,7 @@
 #include <atomic>
 
 #include "kernels.h"
+#include "wave.h"
 
 #pragma clang fp contract(off)
 
@@ -49,8 +50,7 @@ __global__ __launch_bounds__(256) void zcr_kernel(const void* pcm, int pcm_f64, 
     const double a = preemph(pcm, pcm_f64, i - 1, alpha), b = preemph(pcm, pcm_f64, i, alpha);
     cnt += ((a >= 0 && b < 0) || (a < 0 && b >= 0)) ? 1 : 0;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  cnt = wave_sum(cnt);
   if (lane == 0) {
     double r = 0.0;
     if (len >= 2) r = __ddiv_rn((double)cnt, __ddiv_rn((double)len, (double)sr));
@@ -58,25 +58,8 @@ __global__ __launch_bounds__(256) void zcr_kernel(const void* pcm, int pcm_f64, 
   }
 }
 
-// a batched launch's job (blockIdx.y, or blockIdx.x for one-wave kernels) into SGPRs
-template <class J>
-__device__ __forceinline__ J load_job(const J* p) {
-  static_assert(sizeof(J) % 4 == 0, "read as dwords");
-  J r;
-  const int* src = reinterpret_cast<const int*>(p);
-  int* dst = reinterpret_cast<int*>(&r);
-#pragma unroll
-  for (int k = 0; k < (int)(sizeof(J) / 4); ++k) dst[k] = __builtin_amdgcn_readfirstlane(src[k]);
-  return r;
-}
-
-// Phase boundary of a wave-private LDS exchange (see mfcc_pair.hip): DS ops stay on their side,
-// and every DS op of the phase has retired before another lane's words are read or overwritten.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
+// load_job (a batched launch's job: blockIdx.y, or blockIdx.x for one-wave kernels) and
+// wave_lds_sync (the phase boundary of a wave-private LDS exchange) are wave.h's.
 
 // Energy.ComputeShortTimeEnergy (energy.go:25-50) of pre-emphasised frames, every lane one frame:
 // Go's order needs each frame's sum as ONE sequential chain, so the lane count is the frame count.
@@ -170,12 +153,6 @@ __global__ __launch_bounds__(256) void energy_wave_kernel(const void* pcm, int p
 //  * the first tau below the threshold that is a local minimum (:375-384) by a ballot, parabolic
 //    interpolation and the frequency gate (:391-417, 743-764) on uniform values.
 __constant__ double c_yin_win[1024];
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
 
 __global__ __launch_bounds__(256) void yin_kernel(const double* pcm, int64_t n, int64_t f0, int64_t frames, int64_t hop,
                                                   int sr, double* pitch, double* conf, int32_t* tau_out) {

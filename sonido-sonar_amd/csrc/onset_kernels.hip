@@ -21,7 +21,7 @@
 //     by a block scan over the words' population counts.
 //  4. onset_threshold_kernel: AdaptiveThreshold (:200-222), two ordered passes, one lane adding out of LDS.
 //  5. onset_autocorr_kernel: calculateAutocorrelation (tempo_estimation.go:121-150), a lag per lane, the
-//     sum in ascending i as ncc_lags_kernel (align_kernels.hip) does it; onset_autocorr_norm_kernel is
+//     sum in ascending i as ncc_lags_kernel (ncc_kernels.hip) does it; onset_autocorr_norm_kernel is
 //     the reference's in-place "normalisation" (:143-147) written out.
 #include <cstdint>
 

@@ -1,7 +1,7 @@
 // xcorr_api.cpp -- sonar_xcorr_params / sonar_autocorr: CrossCorrelation.Compute and
 // AutoCorrelation.Compute (algorithms/stats/correlation.go:131-200, 669-690) for every correlation
 // type, method and constructor.  The kernels are xcorr_kernels.hip's (Pearson per lag, subtractMean,
-// the FFT method) and align_kernels.hip's (z-score, NCC lag sums); the peak, p-value and quality
+// the FFT method) and ncc_kernels.hip's (z-score, NCC lag sums); the peak, p-value and quality
 // metrics are host::ncc_metrics, as in sonar_ncc.  The signals and the scratch are staged by staging.h;
 // the FFT twiddles are a cached table (ctx.h, cached_table).
 #include <algorithm>

@@ -1,5 +1,5 @@
 // xcorr_kernels.hip -- the configurations of CrossCorrelation.Compute (algorithms/stats/correlation.go)
-// beyond NormalizedCrossCorrelation / TimeDomain (align_kernels.hip), float64 like the Go reference:
+// beyond NormalizedCrossCorrelation / TimeDomain (ncc_kernels.hip), float64 like the Go reference:
 //
 //  xcorr_pearson_kernel   pearsonCorrelation per lag (:314-370): the overlap means in one walk, the
 //                         centred sums in a second one, the clamp to [-1, 1] (NaN passes)
@@ -10,7 +10,7 @@
 //
 // Every sum runs in Go's index order with unfused multiplies and adds (__d*_rn), so the correlations
 // are bit-identical to a sequential float64 evaluation.  The z-score of both inputs (normalize
-// :464-501) and the NCC lag sums are align_kernels.hip's (launch_ncc_zscore, launch_ncc_lags).
+// :464-501) and the NCC lag sums are ncc_kernels.hip's (launch_ncc_zscore, launch_ncc_lags).
 #include <cstdint>
 
 #include "kernels.h"

@@ -1,4 +1,4 @@
-"""CPU model of the DTW backtrack by bands (align_kernels.hip: dtw_exit_map_kernel,
+"""CPU model of the DTW backtrack by bands (dtw_kernels.hip: dtw_exit_map_kernel,
 dtw_walk_chain_kernel, dtw_walk_band_kernel) against the serial backtrack (dtw.go:165-188, the
 one-wave dtw_walk_kernel) on arbitrary direction-code matrices.
 
