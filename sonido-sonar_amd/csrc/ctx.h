@@ -68,7 +68,7 @@ struct sonar_ctx {
   hipEvent_t dtw_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // band | walk | decode boundaries
   double dtw_ms[3] = {0.0, 0.0, 0.0};
   IngestState* ingest = nullptr;
-  std::vector<sonar_ctx*> workers;   // sonar_align_pairs' worker contexts (multi_api.cpp)
+  std::vector<sonar_ctx*> workers;   // sonar_align_pairs' worker contexts (pairs_api.cpp)
   // a second stream for the NCC while the chroma DTW runs on `stream` (align_impl), and the two
   // events that order it: features done -> side, NCC done -> stream
   hipStream_t side = nullptr;

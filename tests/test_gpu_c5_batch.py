@@ -1,6 +1,6 @@
 """BASELINE configs[4] (C5) at its own shape on the product's batched path: sonar_align_pairs with
 its defaults -- 128 pairs in flight = 16 worker streams x batches of 8 pairs, one band-major
-dtw_band_kernel<12, true, false, true> launch per batch (multi_api.cpp align_batch) -- over 128
+dtw_band_kernel<12, true, false, true> launch per batch (pairs_api.cpp enqueue_batch) -- over 128
 pairs of 60 s C5 streams (seed 1000 + k, lag uniform in [0, 20) s), i.e. every
 stream busy at once, as in the bench's C5 leg.
 
