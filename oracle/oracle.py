@@ -349,9 +349,9 @@ class YinTrack:
         if p != 0.0 and self.hist:
             rec = self.hist[-5:]
             if len(rec) >= 3:
-                med = _median_pos(rec)
+                med = np.float64(_median_pos(rec))           # IEEE division below: 0 / 0 is NaN, x / 0 is Inf
                 for r in (0.5, 2.0, 1.0 / 3.0, 3.0):
-                    ex = med * r
+                    ex = med * np.float64(r)
                     with np.errstate(divide="ignore", invalid="ignore"):
                         if abs(p - ex) / ex < 0.1:
                             if abs(p - med) > abs(ex - med):

@@ -1,5 +1,6 @@
 // ctx.h -- internal state behind the opaque sonar_ctx / sonar_result handles,
-// shared by the kernel-level entries (sonar_api.cpp, align_api.cpp, ...) and go_api.cpp (Go-API mirror).
+// shared by the kernel-level entries (sonar_api.cpp, align_api.cpp, ...) and the Go-API mirrors (speech_api.cpp,
+// go_api.cpp).
 #pragma once
 #include "../../include/sonar_gpu.h"
 
@@ -74,7 +75,7 @@ struct sonar_ctx {
   hipStream_t side = nullptr;
   hipEvent_t side_ev[2] = {nullptr, nullptr};
   // the host-PCM pipeline of sonar_extract_speech_features: H2D chunks on `copy`, one event per
-  // chunk the compute streams wait on (go_api.cpp)
+  // chunk the compute streams wait on (speech_api.cpp)
   hipStream_t copy = nullptr;
   std::vector<hipEvent_t> chunk_ev;
   // ... and chunk k's pitch rows on the host (side stream), for the early tracker
@@ -228,3 +229,25 @@ int voice_quality(sonar_ctx* c, const double* dsig, int64_t n, int32_t sr, sonar
     if (e_ != hipSuccess)                                                                    \
       return ::sonar::detail::fail(ctx, SONAR_ERR_DEVICE, std::string(#call ": ") + hipGetErrorString(e_)); \
   } while (0)
+
+namespace sonar {
+namespace detail {
+// c->side and its two events, created on first use (the context's device is current)
+inline int ensure_side(sonar_ctx* c) {
+  if (c->side) return SONAR_OK;
+  HIP_TRY(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+  for (auto& e : c->side_ev) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return SONAR_OK;
+}
+// While one lives, c->stream is the side stream, so a callee that works on c->stream works there.
+// Scope it to the call: the caller's stream is back before the callee's status is looked at.
+struct OnSideStream {
+  sonar_ctx* c;
+  hipStream_t main;
+  explicit OnSideStream(sonar_ctx* ctx) : c(ctx), main(ctx->stream) { c->stream = c->side; }
+  ~OnSideStream() { c->stream = main; }
+  OnSideStream(const OnSideStream&) = delete;
+  OnSideStream& operator=(const OnSideStream&) = delete;
+};
+}  // namespace detail
+}  // namespace sonar

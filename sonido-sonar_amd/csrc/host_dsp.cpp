@@ -215,6 +215,20 @@ void YinTracker::step(double& pitch, double& conf, double& voicing) {
   pitch = p; conf = c; voicing = v;
 }
 
+void track_rows(YinTracker& t, const double* raw_pitch, const double* raw_conf, int64_t lo, int64_t hi, int64_t n,
+                double* pitch, double* conf, double* voicing) {
+  for (int64_t i = lo; i < hi; i++) {
+    double p = 0.0, q = 0.0, v = 0.0;
+    if (i * 512 + 1024 <= n) {
+      p = raw_pitch[i]; q = raw_conf[i];
+      t.step(p, q, v);
+    }
+    if (pitch) pitch[i] = p;
+    if (conf) conf[i] = q;
+    voicing[i] = v;
+  }
+}
+
 CorrSums corr_sums(const double* corr, int64_t nl) {
   CorrSums c;
   c.num_lags = nl;
@@ -407,6 +421,90 @@ double loudness_range_from_rms(std::vector<double> v) {           // energy.go:1
   if (lv <= 0.0) lv = 1e-10;
   if (hv <= 0.0) return 0.0;
   return 20.0 * std::log10(hv / lv);
+}
+
+double percentile10_threshold(const double* e, size_t n) {        // speech.go:594-605 (bubble sort)
+  // the element at index n/10 of the sorted order; a selection gives the same value in O(n)
+  std::vector<double> v(e, e + n);
+  std::nth_element(v.begin(), v.begin() + n / 10, v.end());
+  return v[n / 10];
+}
+
+double silence_ratio(const double* e, size_t n, double thr) {
+  if (!n) return 0.0;
+  int64_t k = 0;
+  for (size_t i = 0; i < n; i++) if (e[i] <= thr) k++;
+  return (double)k / (double)n;
+}
+
+std::vector<double> pause_durations(const double* e, size_t n, double thr, int hop, int rate) {
+  std::vector<double> pauses;
+  const double fts = (double)hop / (double)rate;
+  bool in = false; size_t st = 0;
+  auto close = [&](size_t end) { const double d = (double)(int64_t)(end - st) * fts; if (d > 0.1) pauses.push_back(d); };
+  for (size_t i = 0; i < n; i++) {
+    if (e[i] <= thr) { if (!in) { in = true; st = i; } }
+    else if (in) { close(i); in = false; }
+  }
+  if (in) close(n);                                               // the signal ends in a pause
+  return pauses;
+}
+
+std::vector<int64_t> detect_onsets(const double* e, size_t n) {   // with calculateAdaptiveThreshold :695-716
+  std::vector<int64_t> onsets;
+  if (n < 3) return onsets;
+  std::vector<double> der(n - 1);
+  for (size_t i = 0; i + 1 < n; i++) der[i] = e[i + 1] - e[i];
+  double sum = 0; for (double v : der) sum += v;
+  const double mean = sum / (double)der.size();
+  double var = 0; for (double v : der) { const double d = v - mean; var += d * d; }
+  const double thr = mean + 2 * std::sqrt(var / (double)der.size());
+  for (size_t i = 1; i + 1 < der.size(); i++)
+    if (der[i] > der[i - 1] && der[i] > der[i + 1] && der[i] > thr) onsets.push_back((int64_t)i);
+  return onsets;
+}
+
+std::vector<double> attack_times(const std::vector<int64_t>& onsets, const double* e, int hop, int rate) {
+  std::vector<double> att(onsets.size());
+  const double fts = (double)hop / (double)rate;
+  for (size_t i = 0; i < onsets.size(); i++) {
+    const int64_t on = onsets[i];
+    const double pk = e[on];
+    int64_t st = on;
+    for (int64_t j = on - 1; j >= 0 && j > on - 10; j--) if (e[j] < 0.1 * pk) { st = j; break; }
+    att[i] = (double)(on - st) * fts;
+    if (att[i] > 0.1) att[i] = 0.1;
+  }
+  return att;
+}
+
+double speech_rate(double silence, int64_t n_samples, int rate) {
+  const double dur = (double)n_samples / (double)rate;
+  const double speech_time = dur * (1.0 - silence);
+  return speech_time > 0 ? 4.0 * speech_time / dur : 3.0;
+}
+
+static bool check_periodicity(const double* fr, int64_t n) {      // speech_analysis.go:165-202, first 1024 samples
+  if (n < 1024) return false;
+  double mc = 0.0;
+  for (int lag = 20; lag < 400 && lag < 512; lag++) {
+    double corr = 0.0; int cnt = 0;
+    for (int i = 0; i < 1024 - lag; i++) { corr += fr[i] * fr[i + lag]; cnt++; }
+    if (cnt > 0) { corr /= (double)cnt; if (corr > mc) mc = corr; }
+  }
+  double en = 0.0;
+  for (int i = 0; i < 1024; i++) en += fr[i] * fr[i];
+  en /= 1024.0;
+  if (en > 0) mc /= en;
+  return mc > 0.1;
+}
+
+bool detect_speech(int64_t n_samples, int rate, double crossings, double sum_sq, const double* head, int64_t head_n) {
+  if (n_samples < (int64_t)(rate / 4)) return false;
+  const double z = n_samples <= 1 ? 0.0 : crossings / (double)(n_samples - 1);
+  if (z < 0.01 || z > 0.3) return false;
+  if (std::sqrt(sum_sq / (double)n_samples) < 0.001) return false;
+  return check_periodicity(head, head_n);
 }
 
 }  // namespace host

@@ -1,7 +1,8 @@
 // host_dsp.h -- host-side parts of the hot path that are O(table) or O(path):
 // window / filterbank / DCT tables built once per configuration, and the
-// sequential scalar epilogues of the Go API (YIN temporal tracking, NCC peak
-// metrics, alignment scorers).  Pure C++17, float64, Go evaluation order.
+// sequential scalar epilogues of the Go API (YIN temporal tracking, the speech
+// extractor's tail, NCC peak metrics, alignment scorers).  Pure C++17, float64,
+// Go evaluation order.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -44,6 +45,26 @@ struct YinTracker {
   double prev = 0.0;
   void step(double& pitch, double& conf, double& voicing);
 };
+// DetectPitch's post-processing over the raw YIN rows [lo, hi) of an n-sample signal (frames of 1024
+// every 512; a frame past the end is skipped and gives zeros, pitch_detection.go:226): the tracked
+// pitch, confidence and voicing rows; pitch and conf may be null.  The speech extractor runs its voicing
+// pass (extractVoicingProbability, speech.go:530-550) and then its harmonic pass (:464-509) through the
+// same tracker, whose history carries over: that is the Go behaviour.
+void track_rows(YinTracker& t, const double* raw_pitch, const double* raw_conf, int64_t lo, int64_t hi, int64_t n,
+                double* pitch, double* conf, double* voicing);
+
+// The speech extractor's sequential tail over its energy frames e[0, n) (speech.go:587-797); rate is
+// FeatureConfig.SampleRate, 0 under GenerateFingerprint (F1): the frame time hop / rate is then +Inf.
+// The element at index n / 10 of the sorted energies (n > 0): the silence threshold of the next two
+double percentile10_threshold(const double* e, size_t n);
+double silence_ratio(const double* e, size_t n, double thr);                                  // :641-668
+std::vector<double> pause_durations(const double* e, size_t n, double thr, int hop, int rate);   // :587-639
+std::vector<int64_t> detect_onsets(const double* e, size_t n);                                // :672-716
+std::vector<double> attack_times(const std::vector<int64_t>& onsets, const double* e, int hop, int rate);   // :718-749
+double speech_rate(double silence, int64_t n_samples, int rate);                              // :779-797, speech detected
+// SpeechAnalyzer.detectSpeech (speech_analysis.go:105-202) from the whole signal's zero-crossing count
+// and sum of squares and its first head_n = min(n, 1024) samples (checkPeriodicity reads no more)
+bool detect_speech(int64_t n_samples, int rate, double crossings, double sum_sq, const double* head, int64_t head_n);
 
 // CrossCorrelation metrics from the correlation array (correlation.go:526-667)
 struct NccMetrics {

@@ -28,6 +28,7 @@
 #include "ctx.h"
 #include "host_dsp.h"
 #include "kernels.h"
+#include "speech_layout.h"
 
 namespace sonar {
 namespace detail {
@@ -522,15 +523,9 @@ int64_t sonar_stft_frames(int64_t n, int32_t W, int32_t H) {
   return F <= 0 ? SONAR_ERR_TOO_SHORT : F;
 }
 
-int64_t sonar_energy_frames(int64_t n, int32_t W, int32_t H) {
-  if (n < W || H <= 0 || W <= 0) return 0;
-  return (n - W) / H + 1;
-}
+int64_t sonar_energy_frames(int64_t n, int32_t W, int32_t H) { return sonar::energy_frames(n, W, H); }
 
-int64_t sonar_pitch_frames(int64_t n) {
-  const int64_t F = (n - 1024) / 512 + 1;
-  return F < 0 ? 0 : F;
-}
+int64_t sonar_pitch_frames(int64_t n) { return sonar::pitch_frames(n); }
 
 void sonar_fp_cfg_default(sonar_fp_cfg* c) {
   std::memset(c, 0, sizeof(*c));

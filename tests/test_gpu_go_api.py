@@ -7,6 +7,7 @@ import pytest
 
 import oracle as O
 import sonar
+import speech_tail_ref as R
 from parity import assert_mfcc, assert_rel, assert_rolloff
 from sonar import synth
 
@@ -172,3 +173,72 @@ def test_generate_fingerprint_early_tracker_equals_late(ctx, monkeypatch):
     assert early.keys() == late.keys()
     for k in early:
         assert np.array_equal(np.asarray(early[k]), np.asarray(late[k]), equal_nan=True), k
+
+
+# ---- the sequential host tail and the tracker on a voiced, gated signal -----------------------------
+
+_TAIL_FC = dict(window_size=512, hop_size=128, stft_window_size=512, stft_hop_size=128, enable_mfcc=1,
+                enable_speech_features=1, enable_temporal_features=1, mfcc_coefficients=13)
+_TAIL_REF = {}
+
+
+def _tail_reference(csr):
+    """(signal, pre-emphasised signal, |X| rows, oracle composition) per FeatureConfig.SampleRate, computed once."""
+    if csr not in _TAIL_REF:
+        x = R.gated_tone()
+        _TAIL_REF[csr] = (x, O.preemphasis(x, 0.97), O.stft_mag(x, 512, 128, nthreads=8),
+                          O.speech_features_reference(x, 16000, dict(sample_rate=csr, **_TAIL_FC)))
+    return _TAIL_REF[csr]
+
+
+def _same(a, b):
+    return np.array_equal(np.asarray(a, float).reshape(-1), np.asarray(b, float).reshape(-1), equal_nan=True)
+
+
+@pytest.mark.parametrize("chunk", [None, 20011])
+@pytest.mark.parametrize("csr", [16000, 0])
+def test_speech_tail_and_tracker_on_voiced_gated_tone(ctx, csr, chunk, monkeypatch):
+    """The host tail (silence ratio, pauses, onsets, attack times, speech rate) against the plain-Python
+    checker on the returned energies, exactly; the pitch rows with a tracker that sees nonzero pitches
+    and carries its state from the voicing pass into the harmonic pass; the whole-signal amplitudes.
+    SampleRate 0 is GenerateFingerprint's F1 case: the frame time is +Inf, so pauses are +Inf, attack
+    times NaN or 0.1 and the speech rate NaN.  Chunk 20011: two chunks, neither seam on a frame boundary."""
+    x, pre, mag, ref = _tail_reference(csr)
+    n = len(x)
+    # what keeps this from being vacuous, on the reference at the real rate
+    r16 = _tail_reference(16000)[3]
+    assert r16["is_speech"] == 1.0
+    assert np.count_nonzero(r16["pitch_estimate"]) == 48 and len(r16["pitch_estimate"]) == 61
+    assert np.count_nonzero(r16["voicing_probability"]) == 40
+    fresh = O.pitch_track(_tail_reference(16000)[1], 16000, 1)[0]       # one pass of a fresh tracker
+    assert not np.array_equal(fresh, r16["pitch_estimate"])              # the shared state is visible
+    e16 = [float(v) for v in r16["short_time_energy"]]
+    assert len(e16) == 247 and R.detect_onsets(e16) == [61, 124, 186]
+    assert R.pause_durations(e16, 128, 16000) == [0.12] * 4
+    assert np.count_nonzero(R.attack_times(R.detect_onsets(e16), e16, 128, 16000)) == 3
+
+    if chunk is None:
+        monkeypatch.delenv("SONAR_PCM_CHUNK", raising=False)
+    else:
+        monkeypatch.setenv("SONAR_PCM_CHUNK", str(chunk))
+    got = ctx.extract_speech_features(x, 16000, ctx.feature_config(sample_rate=csr, is_news=0, precision=sonar.F64,
+                                                                    **_TAIL_FC))
+    assert got["is_speech"] == ref["is_speech"] == 1.0
+    _cmp(got, ref, 1e-6, mag=mag)
+    for k in ("pitch_estimate", "pitch_confidence", "voicing_strength", "voicing_probability", "short_time_energy"):
+        assert np.array_equal(got[k], ref[k]), k
+    assert np.array_equal(got["rms_energy"], got["short_time_energy"])
+    e = [float(v) for v in np.asarray(got["short_time_energy"]).reshape(-1)]
+    onsets = R.detect_onsets(e)
+    assert _same(got["silence_ratio"], [R.silence_ratio(e)])
+    assert _same(got["pause_duration"], R.pause_durations(e, 128, csr))
+    assert _same(got["onset_density"], [R.onset_density(onsets, n, 16000)])
+    assert _same(got["attack_time"], R.attack_times(onsets, e, 128, csr))
+    assert _same(got["speech_rate"], [R.speech_rate(e, n, csr, True)])
+    assert _same(got["peak_amplitude"], [np.max(np.abs(pre))])
+    seq = 0.0
+    for v in np.abs(pre):
+        seq += float(v)
+    avg = float(np.asarray(got["average_amplitude"]).reshape(-1)[0])
+    print("average_amplitude", avg, seq / n, abs(avg - seq / n) / (seq / n), 2 * n * 2.0 ** -53)
+    assert abs(avg - seq / n) <= 2 * n * 2.0 ** -53 * (seq / n)
