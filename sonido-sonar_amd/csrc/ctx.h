@@ -1,6 +1,6 @@
 // ctx.h -- internal state behind the opaque sonar_ctx / sonar_result handles,
-// shared by the kernel-level entries (sonar_api.cpp, align_api.cpp, ...) and the Go-API mirrors (speech_api.cpp,
-// go_api.cpp).
+// shared by the kernel-level entries (sonar_api.cpp, fp_api.cpp, align_api.cpp, ...) and the Go-API mirrors
+// (speech_api.cpp, go_api.cpp).
 #pragma once
 #include "../../include/sonar_gpu.h"
 
@@ -25,7 +25,10 @@ struct DevBuf {
   int64_t tag = 0;
 };
 
+// Cached tables of the fingerprint paths and the chroma kernel: ONE device allocation each (base, the
+// upload of a host image of fp_tables.h; sonar_destroy frees it) and typed views into it.
 struct FpTables {
+  void* base = nullptr;
   void* window = nullptr;
   int *mel_lo = nullptr, *mel_hi = nullptr, *mel_woff = nullptr, *grp_off = nullptr, *grp_mels = nullptr;
   void *mel_w = nullptr, *dct = nullptr, *lift = nullptr;
@@ -36,6 +39,7 @@ struct FpTables {
 // tables of the headline kernel (mfcc_pair.hip); ok = false -> configuration unsupported there
 struct PairTables {
   bool ok = false;
+  void* base = nullptr;
   // [0] float32 tables (the headline), [1] float64 (the same bank at the reference's precision; its
   // own chunk lane order, searched for its 16-byte power-row reads)
   void *window[2] = {}, *tw1[2] = {}, *tw2[2] = {}, *chunk_w[2] = {}, *dct[2] = {};
@@ -50,6 +54,7 @@ struct IngestState;  // pinned slots + host pool of sonar_ingest_f64le (ingest_a
 
 struct sonar_ctx {
   int device = 0;
+  int cus = 256;   // the device's compute units (sonar_create); the launch geometry of the fused kernels
   hipStream_t own = nullptr;
   hipStream_t stream = nullptr;
   std::string err;
@@ -57,7 +62,7 @@ struct sonar_ctx {
   std::map<std::string, DevBuf> hbufs;   // pinned host staging (hipHostMalloc)
   std::map<std::string, FpTables> fp_tables;
   std::map<std::string, PairTables> pair_tables;
-  struct ChromaT { void* win; void* trig; void* map; void* cls; };
+  struct ChromaT { void* base; void* win; void* trig; void* map; void* cls; };
   std::map<std::string, ChromaT> chroma_tables;
   bool timing = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;   // spare pair (kept for ABI simplicity)
@@ -151,6 +156,9 @@ void* hbuf(sonar_ctx* c, const std::string& name, size_t bytes);
 std::shared_ptr<void> pinned_block(size_t bytes);
 // frees the pool's idle blocks (sonar_trim)
 void pinned_pool_trim();
+// A host image of tables (fp_tables.h) as one device allocation: one hipMalloc and one blocking
+// hipMemcpy; null, with nothing left allocated, when either fails (fp_api.cpp)
+void* upload_image(const std::vector<unsigned char>& image);
 // chroma tables of frame size fs at sample rate sr, built once per context (sonar_api.cpp); null on
 // allocation failure
 const sonar_ctx::ChromaT* chroma_tables_for(sonar_ctx* c, int fs, int sr);
@@ -204,7 +212,7 @@ int detect_content_type(sonar_ctx* c, const double* pcm, int64_t n, int32_t sr, 
 void timed_end(sonar_ctx* c, hipStream_t s, hipEvent_t end);
 // frees the ingest ring and joins its host threads (ingest_api.cpp)
 void ingest_release(sonar_ctx* c);
-// sonar_fingerprint with the PCM already on the device and host outputs (sonar_api.cpp)
+// sonar_fingerprint with the PCM already on the device and host outputs (fp_api.cpp)
 // [f_lo, f_hi): only those frames of the whole signal's STFT (device outputs, per-frame kernel)
 // raw_window: the window table is not energy-normalised (HarmonicProduct.applyWindow, sonar_hps); a
 // table of its own under its own cache key, the kernels are the same

@@ -1,6 +1,6 @@
 """The LDS bank-conflict model behind mfcc_pair_kernel's float64 layout (tools/pair_lds_model.py,
 DESIGN.md Kernel 1a "LDS re-laid for 16-byte accesses"), and the layout constants the kernel and
-the host tables share (csrc/kernels.h).  Layout-only phases need no filterbank, so the synthetic
+the host tables share (csrc/mfcc_pair_layout.h).  Layout-only phases need no filterbank, so the synthetic
 chunk table below keeps this test fast; the measured counterparts are profiles/r06ap_* / r06aq_*."""
 import os
 import re
@@ -52,7 +52,7 @@ def test_float32_layout_unchanged():
 
 
 def test_kernel_constants_match_the_model():
-    src = open(os.path.join(ROOT, "sonido-sonar_amd", "csrc", "kernels.h")).read()
+    src = open(os.path.join(ROOT, "sonido-sonar_amd", "csrc", "mfcc_pair_layout.h")).read()
     assert re.search(r"mfcc_pair_pad_rows\(int f64\) \{ return f64 \? 1 : 2; \}", src)
     assert re.search(r"mfcc_pair_dct_pad\(int f64\) \{ return f64 \? 2 : 4; \}", src)
     assert re.search(r"kPairTw2Row = 9;", src)

@@ -43,7 +43,7 @@ def test_weight_stride_rule(J):
 def test_weight_stride_values_and_kernel_source():
     got = {J: M.weight_stride(J) for J in range(9, 17)}
     assert got == {9: 10, 10: 10, 11: 14, 12: 14, 13: 14, 14: 14, 15: 18, 16: 18}
-    src = open(os.path.join(ROOT, "sonido-sonar_amd", "csrc", "kernels.h")).read()
+    src = open(os.path.join(ROOT, "sonido-sonar_amd", "csrc", "mfcc_pair_layout.h")).read()
     body = re.search(r"constexpr int mfcc_pair_w_stride\(int J, int f64\) \{(.*?)\n\}", src, re.S).group(1)
     assert "return J | 1;" in body and "J + (J & 1)" in body and "(m & 3) == 2 ? m : m + 2" in body
 

@@ -9,7 +9,8 @@ cycles the lane groups of each kind cost, with the banking table of MI355X_MICRO
   write_b32  2 x 32, mod 32   write_b64 4 x 16 contiguous, mod 32   write_b128 8 x 8 contiguous, mod 32
 Extra cycles of a group = (most distinct dwords on one bank) - 1, summed over groups -- the
 quantity SQ_LDS_BANK_CONFLICT counts.  The chunk tables (lane order, sources) are rebuilt here as
-build_pair_tables (csrc/sonar_api.cpp) builds them, from the oracle's filterbank.
+build_pair_tables (csrc/fp_tables.cpp) builds them, from the oracle's filterbank; tests/test_fp_tables_cpu.py
+compares the two.
 
 The float32 kernel's reads are priced in the forms it issues (paired_reads=False: sixteen single
 T2 reads, filterbank weights two bins per ds_read_b128 at the row stride weight_stride(J)) or in the
@@ -65,7 +66,7 @@ COST = {"read_b32": 2, "read_b64": 2, "read_b128": 4, "read2_b64": 8, "read2st64
 
 
 def weight_stride(J, f64=False):
-    """chunk_w row stride in complex (csrc/kernels.h mfcc_pair_w_stride): float32 rows are read 16
+    """chunk_w row stride in complex (csrc/mfcc_pair_layout.h mfcc_pair_w_stride): float32 rows are read 16
     bytes at a time, so the stride is even, >= J (J + 1 for odd J) and = 2 mod 4 -- rows 16-byte
     aligned, lanes an odd number of 16-byte units apart; float64 keeps J | 1"""
     if f64:
