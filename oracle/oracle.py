@@ -220,7 +220,8 @@ VOICE_QUALITY_KEYS = ("jitter", "shimmer", "hnr", "noise_measure", "f0_stability
 def voice_quality(signal, sample_rate):
     """VoiceQualityAnalyzer.AnalyzeVoiceQuality (algorithms/speech/voice_quality.go:56-111).
     Returns (dict, status): status 0 ok, -1 shorter than one second, -2 fewer than 3 periods
-    (the Go call returns an error and a nil result; the dict is then all zero)."""
+    (the Go call returns an error and a nil result; the dict is then all zero, but for num_periods
+    at status -2: the count the error text names)."""
     signal = _f64(signal)
     out = np.zeros(12)
     st = lib().or_voice_quality(_p(signal), len(signal), sample_rate, _p(out))

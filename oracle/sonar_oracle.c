@@ -635,7 +635,7 @@ int or_voice_quality(const double* sig, int64_t n, int sr, double* out) {
     double vstr = 0.0;
     if (n == 1024) { double p, c; or_yin_raw(sig, sr, &p, &c, NULL); yin_track_step(&st, &p, &c, &vstr); }
     int rc = 0;
-    if (np_ < 3) { rc = -2; goto done; }
+    if (np_ < 3) { rc = -2; out[8] = (double)np_; goto done; }   /* the count Go's error text names (:67-69) */
     {
         double* amp = (double*)malloc(sizeof(double) * np_);
         for (int64_t k = 0; k < np_; k++) {                       /* RMS per period :200-207 */

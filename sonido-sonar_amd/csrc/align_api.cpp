@@ -1,7 +1,7 @@
 // align_api.cpp -- the alignment entries of include/sonar_gpu.h: sonar_ncc and the sonar_dtw
 // family (CrossCorrelation.Compute's NCC, correlation.go:131-409; DTWAlignment.Align, dtw.go:55-307),
 // and their deferred-sync halves for one stream pair (ncc_enqueue, dtw_enqueue / dtw_finish: the
-// device path of go_api.cpp's align_impl).  The kernels are ncc_kernels.hip's and dtw_kernels.hip's.
+// device path of align_extract_api.cpp's align_impl).  The kernels are ncc_kernels.hip's and dtw_kernels.hip's.
 #include "../../include/sonar_gpu.h"
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,6 @@
-// go_api.cpp -- C++ restatement of the Go orchestration above the GPU seams, alignment half
-// (the speech extractor and GenerateFingerprint are speech_api.cpp's).
+// align_extract_api.cpp -- the alignment extractor: C++ restatement of the Go orchestration above the
+// GPU seams (the speech extractor and GenerateFingerprint are speech_api.cpp's, the music extractor
+// and its energy + chroma music_api.cpp's).
 //
 //   sonar_align_features            AlignmentExtractor.ExtractAlignmentFeatures
 //                                   (fingerprint/extractors/alignment.go:139-476)
@@ -14,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -23,61 +25,7 @@
 
 using sonar::detail::dbuf;
 using sonar::detail::fail;
-
-namespace {
-// MusicFeatureExtractor energy + chroma (music.go:245-259, :327-376, :460-466) on c->stream; `tag`
-// names this call's scratch, so two calls on different streams do not share it
-int music_features_impl(sonar_ctx* c, const double* pcm, int64_t n, int32_t sr, int32_t stft_w, int32_t stft_h,
-                        int32_t fw, int32_t fh, double* energy, double* chroma, int32_t device_ptrs,
-                        const std::string& tag) {
-  if (!c) return SONAR_ERR_INVALID;
-  if (!pcm || n <= 0) return fail(c, SONAR_ERR_INVALID, "invalid input data");        // music.go:179-181
-  if (stft_w <= 0 || stft_h <= 0) return fail(c, SONAR_ERR_INVALID, "window and hop size must be positive");
-  const int64_t F = sonar_stft_frames(n, stft_w, stft_h);
-  if (F <= 0) return fail(c, SONAR_ERR_TOO_SHORT, "signal too short for given window size and hop size");
-  if (fh <= 0) return fail(c, SONAR_ERR_INVALID, "hop size must be positive");
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const double* dp = pcm;
-  if (!device_ptrs) {
-    void* b = dbuf(c, "mf.pcm" + tag, n * 8);
-    if (!b) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(b, pcm, n * 8, hipMemcpyHostToDevice, s));
-    dp = (const double*)b;
-  }
-  double* y = (double*)dbuf(c, "mf.pre" + tag, n * 8);           // processedPCM
-  if (!y) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-  double* dcs = (double*)dbuf(c, "mf.dcscratch" + tag, sonar::dc_preemph_scratch_bytes(n));
-  if (!dcs) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-  if (sonar::launch_dc_preemph(dp, n, 0.995, 0.95, y, dcs, s) != 0) return fail(c, SONAR_ERR_DEVICE, "dc launch failed");
-  const int64_t Fe = sonar_energy_frames(n, fw, fh);
-  double* de = device_ptrs ? energy : (double*)dbuf(c, "mf.energy" + tag, std::max<int64_t>(Fe, 1) * 8);
-  // ShortTimeEnergy of the already pre-emphasised signal: alpha 0 makes the kernel's
-  // pre-emphasis the identity (x - 0 * x[n-1] == x exactly)
-  if (Fe > 0 && sonar::launch_energy(y, 1, n, Fe, fw, fh, 0.0, de, 1, s) != 0)
-    return fail(c, SONAR_ERR_DEVICE, "energy launch failed");
-  double* dc = device_ptrs ? chroma : (double*)dbuf(c, "mf.chroma" + tag, F * 12 * 8);
-  if (!de || !dc) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-  const int rc = sonar_chroma_stft(c, y, n, F, fh, sr, 0, dc, 1);
-  if (rc != SONAR_OK) return rc;
-  if (!device_ptrs) {
-    if (Fe > 0) HIP_TRY(c, hipMemcpyAsync(energy, de, Fe * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(chroma, dc, F * 12 * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-  }
-  return SONAR_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int sonar_music_alignment_features(sonar_ctx* c, const double* pcm, int64_t n, int32_t sr, int32_t stft_w,
-                                   int32_t stft_h, int32_t fw, int32_t fh, double* energy, double* chroma,
-                                   int32_t device_ptrs) {
-  return music_features_impl(c, pcm, n, sr, stft_w, stft_h, fw, fh, energy, chroma, device_ptrs, "");
-}
-
-}  // extern "C"
+using sonar::detail::music_features_impl;
 
 namespace sonar {
 namespace detail {
@@ -264,9 +212,9 @@ int align_impl(sonar_ctx* c, const double* qe, int64_t nqe, const double* re, in
     if (rc != SONAR_OK) return rc;
     in.has_dtw = true; in.nqc = nqc; in.nrc = nrc;
   }
-  auto* res = new sonar_result();
-  sonar::detail::align_finish(in, res, nullptr);
-  *out = res;
+  std::unique_ptr<sonar_result> res(new sonar_result());
+  sonar::detail::align_finish(in, res.get(), nullptr);
+  *out = res.release();
   return SONAR_OK;
 }
 
@@ -304,11 +252,11 @@ int sonar_align_pair_device(sonar_ctx* c, const double* q_pcm, int64_t nq, const
   if (const int rc = sonar::detail::ensure_side(c)) return rc;
   HIP_TRY(c, hipEventRecord(c->side_ev[0], c->stream));        // the caller's PCM is ready on c->stream
   HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_ev[0], 0));
-  int st = music_features_impl(c, q_pcm, nq, sample_rate, stft_window, hop, feature_window, hop, qe, qc, 1, "");
+  int st = music_features_impl(c, q_pcm, nq, sample_rate, stft_window, hop, feature_window, hop, qe, qc, 1, "mf.");
   if (st != SONAR_OK) return st;
   {
     sonar::detail::OnSideStream on_side(c);
-    st = music_features_impl(c, r_pcm, nr, sample_rate, stft_window, hop, feature_window, hop, re, rc, 1, ".r");
+    st = music_features_impl(c, r_pcm, nr, sample_rate, stft_window, hop, feature_window, hop, re, rc, 1, "mf.r.");
   }
   if (st != SONAR_OK) return st;
   HIP_TRY(c, hipEventRecord(c->side_ev[1], c->side));

@@ -6,19 +6,17 @@
 
 #include <algorithm>
 #include <cctype>
-#include <cmath>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <vector>
 
 #include "ctx.h"
-#include "go_math.h"
+#include "host_dsp.h"
 #include "kernels.h"
+#include "staging.h"
 
-using sonar::go_max;
-using sonar::detail::dbuf;
 using sonar::detail::fail;
+using sonar::detail::Staging;
 
 namespace {
 
@@ -92,12 +90,48 @@ int from_metadata(const char* ct, const char* genre, const char* station, const 
   return infer_from_station(station ? station : "", url ? url : "");
 }
 
+// What detect_from_audio derives from the sample count and rate: the DFT's size, the frame counts, and the
+// sections of its one scratch block, the same on the device and in its host copy: the scan's three 64-bit
+// words (sign changes, max |x|, min |x|) in 64 bytes, the K magnitudes, the fe sums of squares of frames
+// 1024 / 512 and the ft of frames of 100 ms.
+struct ContentPlan {
+  static constexpr size_t kWords = 8;         // doubles
+  int N, K;
+  int64_t fe, ts, ft;
+  ContentPlan(int64_t n, int32_t sr)
+      : N((int)std::min<int64_t>(2048, n)), K(N / 2 + 1),
+        fe(n > 1024 ? (n - 1024 + 511) / 512 : 0),                 // i < n - 1024, i += 512
+        ts(sr / 10), ft(n > ts ? (n - ts + ts - 1) / ts : 0) {}    // i < n - ts, i += ts
+  size_t doubles() const { return kWords + (size_t)(K + fe + ft); }
+  template <typename D> D* mag(D* block) const { return block + kWords; }
+  template <typename D> D* esum(D* block) const { return mag(block) + K; }
+  template <typename D> D* tsum(D* block) const { return esum(block) + fe; }
+};
+
+// the PCM to the device, the four launches, and the block's copy into `host`, all queued on c->stream
+int scan(sonar_ctx* c, const double* pcm, int64_t n, const ContentPlan& p, double* host) {
+  hipStream_t s = c->stream;
+  Staging st{c, "cd.", false};
+  const double* x = st.in("pcm", pcm, n);
+  double* w = st.tmp<double>("work", p.doubles());
+  if (const int rc = st.ready("device allocation failed")) return rc;
+  hipEvent_t tend = sonar::detail::timed_begin(c, s);
+  if (sonar::launch_detect_scan(x, n, reinterpret_cast<unsigned long long*>(w), s) ||
+      sonar::launch_frame_sums(x, n, p.fe, 512, 1024, p.esum(w), s) ||
+      sonar::launch_frame_sums(x, n, p.ft, p.ts, p.ts, p.tsum(w), s) || sonar::launch_dft_mag(x, p.N, p.mag(w), s))
+    return fail(c, SONAR_ERR_DEVICE, "content detection launch failed");
+  sonar::detail::timed_end(c, s, tend);
+  HIP_TRY(c, hipMemcpyAsync(host, w, p.doubles() * sizeof(double), hipMemcpyDeviceToHost, s));
+  return SONAR_OK;
+}
+
 }  // namespace
 
 namespace sonar {
 namespace detail {
 
-// DetectFromAudio (:72-101) + extractAcousticFeatures (:118-150) + classifyFromFeatures (:153-217)
+// DetectFromAudio (:72-101): extractAcousticFeatures (:118-150) and classifyFromFeatures (:153-217) are
+// host_dsp.cpp's, over what the four launches below leave in the scratch block
 int detect_from_audio(sonar_ctx* c, const double* pcm, int64_t n, int32_t sr, double thr, int32_t* out,
                       sonar_acoustic_features* feat) {
   sonar_acoustic_features f;
@@ -109,129 +143,22 @@ int detect_from_audio(sonar_ctx* c, const double* pcm, int64_t n, int32_t sr, do
   }
   if (sr < 10) return fail(c, SONAR_ERR_INVALID, "sample rate below 10 Hz: the 100 ms frame loop of "
                                                  "calculateTemporalStability never ends (content_detector.go:392-402)");
-  hipStream_t s = c->stream;
-  const int N = (int)std::min<int64_t>(2048, n), K = N / 2 + 1;
-  const int64_t fe = n > 1024 ? (n - 1024 + 511) / 512 : 0;               // i < n - 1024, i += 512
-  const int64_t ts = sr / 10;
-  const int64_t ft = n > ts ? (n - ts + ts - 1) / ts : 0;                  // i < n - ts, i += ts
-  double* x = static_cast<double*>(dbuf(c, "cd.pcm", n * sizeof(double)));
-  char* w = static_cast<char*>(dbuf(c, "cd.work", 64 + (K + fe + ft) * sizeof(double)));
-  if (!x || !w) return fail(c, SONAR_ERR_NOMEM, "device allocation failed");
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(w);
-  double* mag = reinterpret_cast<double*>(w + 64);
-  double* esum = mag + K;
-  double* tsum = esum + fe;
-  HIP_TRY(c, hipMemcpyAsync(x, pcm, n * sizeof(double), hipMemcpyHostToDevice, s));
-  hipEvent_t tend = timed_begin(c, s);
-  if (launch_detect_scan(x, n, words, s) || launch_frame_sums(x, n, fe, 512, 1024, esum, s) ||
-      launch_frame_sums(x, n, ft, ts, ts, tsum, s) || launch_dft_mag(x, N, mag, s))
-    return fail(c, SONAR_ERR_DEVICE, "content detection launch failed");
-  timed_end(c, s, tend);
-  std::vector<double> h(K + fe + ft);
-  unsigned long long hw[3];
-  HIP_TRY(c, hipMemcpyAsync(hw, words, sizeof(hw), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(h.data(), mag, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  const double* spec = h.data();
-  const double* es = spec + K;
-  const double* tsm = es + fe;
-  // calculateZeroCrossingRate (:220-233)
-  f.zero_crossing_rate = n <= 1 ? 0.0 : (double)hw[0] / (double)(n - 1);
-  // calculateSpectralCentroid (:236-252)
-  {
-    double ws = 0.0, ms = 0.0;
-    for (int i = 0; i < K; i++) {
-      const double fr = (double)i * (double)sr / (double)(K * 2);
-      ws += fr * spec[i];
-      ms += spec[i];
-    }
-    f.spectral_centroid = ms == 0 ? 0.0 : ws / ms;
-  }
-  // calculateEnergyVariance (:255-290)
-  if (n >= 2048 && fe > 1) {
-    double mean = 0.0;
-    for (int64_t i = 0; i < fe; i++) mean += es[i] / 1024.0;
-    mean /= (double)fe;
-    double var = 0.0;
-    for (int64_t i = 0; i < fe; i++) {
-      const double d = es[i] / 1024.0 - mean;
-      var += d * d;
-    }
-    f.energy_variance = var / (double)fe;
-  }
-  // calculateSilenceRatio (:293-317)
-  if (fe > 0) {
-    int64_t silent = 0;
-    for (int64_t i = 0; i < fe; i++) silent += std::sqrt(es[i] / 1024.0) < 0.01;
-    f.silence_ratio = (double)silent / (double)fe;
-  }
-  // calculateDynamicRange (:320-343)
-  {
-    double mx, mn;
-    std::memcpy(&mx, &hw[1], 8);
-    std::memcpy(&mn, &hw[2], 8);
-    f.dynamic_range = (mn == 0 || std::isinf(mn)) ? 0.0 : 20.0 * std::log10(mx / mn);
-  }
-  // calculateFreqEnergyRatio (:346-369)
-  {
-    const int split = K / 4;
-    double lo = 0.0, hi = 0.0;
-    for (int i = 0; i < split && i < K; i++) lo += spec[i] * spec[i];
-    for (int i = split; i < K; i++) hi += spec[i] * spec[i];
-    const double tot = lo + hi;
-    if (tot != 0) { f.low_freq_energy = lo / tot; f.high_freq_energy = hi / tot; }
-  }
-  // calculateHarmonicRatio (:372-401)
-  if (K >= 10) {
-    std::vector<int> peaks;
-    for (int i = 2; i < K - 2; i++)
-      if (spec[i] > spec[i - 1] && spec[i] > spec[i + 1] && spec[i] > spec[i - 2] && spec[i] > spec[i + 2])
-        peaks.push_back(i);
-    if (peaks.size() >= 2) {
-      int harm = 0;
-      for (size_t q = 1; q < peaks.size(); q++) {
-        const double r = (double)peaks[q] / (double)peaks[0];
-        if (std::fabs(r - std::round(r)) < 0.1) harm++;
-      }
-      f.harmonic_ratio = (double)harm / (double)(peaks.size() - 1);
-    }
-  }
-  // calculateTemporalStability (:404-447)
-  if (n >= 3 * ts && ft > 1) {
-    double mean = 0.0;
-    for (int64_t i = 0; i < ft; i++) mean += tsm[i];
-    mean /= (double)ft;
-    if (mean != 0) {
-      double var = 0.0;
-      for (int64_t i = 0; i < ft; i++) {
-        const double d = tsm[i] - mean;
-        var += d * d;
-      }
-      var /= (double)ft;
-      f.temporal_stability = go_max(0.0, 1.0 - std::sqrt(var) / mean);
-    }
-  }
-  // classifyFromFeatures (:153-217); map order in Go, fixed order here
-  double music = 0.0, speech = 0.0, sports = 0.0;
-  if (f.zero_crossing_rate < 0.1) music += 2.0;
-  if (f.harmonic_ratio > 0.3) music += 2.0;
-  if (f.temporal_stability > 0.5) music += 1.0;
-  if (f.dynamic_range > 20) music += 1.0;
-  if (f.zero_crossing_rate > 0.05 && f.zero_crossing_rate < 0.3) speech += 2.0;
-  if (f.spectral_centroid > 800 && f.spectral_centroid < 3000) speech += 2.0;
-  if (f.harmonic_ratio < 0.2) speech += 1.0;
-  if (f.silence_ratio > 0.1 && f.silence_ratio < 0.4) speech += 1.0;
-  if (f.energy_variance > 0.3) sports += 2.0;
-  if (f.dynamic_range > 30) sports += 1.5;
-  if (f.temporal_stability < 0.4) sports += 1.0;
-  const int types[4] = {SONAR_CT_MUSIC, SONAR_CT_NEWS, SONAR_CT_TALK, SONAR_CT_SPORTS};
-  const double scores[4] = {music, speech, speech * 0.9, sports};
-  int best = SONAR_CT_UNKNOWN;
-  double bs = thr;
-  for (int i = 0; i < 4; i++)
-    if (scores[i] > bs) { bs = scores[i]; best = types[i]; }
-  f.classification_confidence = bs / 6.0;
-  *out = best;
+  const ContentPlan p(n, sr);
+  std::vector<double> h(p.doubles());         // the block on the host
+  sonar::detail::DrainOnExit drain{c};        // declared after h: an early exit waits for the copy into it
+  if (const int rc = scan(c, pcm, n, p, h.data())) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  drain.armed = false;
+  unsigned long long crossings;
+  double mx, mn;
+  std::memcpy(&crossings, h.data(), 8);
+  std::memcpy(&mx, h.data() + 1, 8);
+  std::memcpy(&mn, h.data() + 2, 8);
+  f = sonar::host::content_features(crossings, mx, mn, p.mag(h.data()), p.K, p.esum(h.data()), p.fe,
+                                    p.tsum(h.data()), p.ft, n, sr);
+  const sonar::host::ContentClass cls = sonar::host::classify_content(f, thr);
+  f.classification_confidence = cls.confidence;
+  *out = cls.type;
   if (feat) *feat = f;
   return SONAR_OK;
 }

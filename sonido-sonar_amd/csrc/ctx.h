@@ -1,6 +1,6 @@
 // ctx.h -- internal state behind the opaque sonar_ctx / sonar_result handles,
 // shared by the kernel-level entries (sonar_api.cpp, fp_api.cpp, align_api.cpp, ...) and the Go-API mirrors
-// (speech_api.cpp, go_api.cpp).
+// (speech_api.cpp, align_extract_api.cpp).
 #pragma once
 #include "../../include/sonar_gpu.h"
 
@@ -166,10 +166,11 @@ const sonar_ctx::ChromaT* chroma_tables_for(sonar_ctx* c, int fs, int sr);
 inline int64_t ncc_max_lag(int64_t max_lag, int64_t na, int64_t nb) {
   return std::max<int64_t>(std::min({max_lag, na - 1, nb - 1}), 0);
 }
-// NCC + chroma DTW of one stream pair with two stream synchronisations (align_impl's device
-// path, align_api.cpp): ncc_enqueue and dtw_enqueue only launch and queue their small results
-// into pinned host memory; after one hipStreamSynchronize, ncc_metrics_host reads the
-// correlation and dtw_finish decodes the warping path into pinned host arrays (second sync).
+// NCC + chroma DTW of one stream pair with two stream synchronisations (the device path of
+// align_extract_api.cpp's align_impl; defined in align_api.cpp): ncc_enqueue and dtw_enqueue only
+// launch and queue their small results into pinned host memory; after one hipStreamSynchronize,
+// ncc_metrics_host reads the correlation and dtw_finish decodes the warping path into pinned host
+// arrays (second sync).
 struct DtwPending {
   sonar::DtwArgs a{};      // the queued DTW: its sequences, geometry and scratch (dtw_scratch)
   int64_t* st = nullptr;   // pinned: [0] path length, [1] sync words 0..1, [2] non-finite flag
@@ -184,7 +185,7 @@ int dtw_enqueue(sonar_ctx* c, const double* dq, int64_t nq, const double* dr, in
                 DtwPending* p);
 int dtw_finish(sonar_ctx* c, DtwPending* p, const int32_t** hq, const int32_t** hr, const double** hc, int64_t* P,
                double* distance);
-// ExtractAlignmentFeatures' host tail over the GPU results of one pair (go_api.cpp): the scorers,
+// ExtractAlignmentFeatures' host tail over the GPU results of one pair (align_extract_api.cpp): the scorers,
 // selectBestAlignment and the time-stretch estimate, into a result handle and/or a pair record
 struct AlignIn {
   const double* corr = nullptr;   // energy correlation, 2L+1 lags (null: no correlation candidate)
@@ -200,6 +201,10 @@ struct AlignIn {
   int32_t sample_rate = 0, hop = 0;
 };
 void align_finish(const AlignIn& in, sonar_result* res, sonar_pair_record* rec);
+// sonar_music_alignment_features (music_api.cpp); `tag` prefixes the names of the call's scratch, so the
+// two streams of sonar_align_pair_device keep their own
+int music_features_impl(sonar_ctx* c, const double* pcm, int64_t n, int32_t sr, int32_t stft_w, int32_t stft_h,
+                        int32_t fw, int32_t fh, double* energy, double* chroma, int32_t device_ptrs, const char* tag);
 hipEvent_t timed_begin(sonar_ctx* c, hipStream_t s);
 // the context a comparator gallery lives on (compare_api.cpp)
 sonar_ctx* gallery_ctx(const sonar_gallery* g);
@@ -256,6 +261,20 @@ struct OnSideStream {
   ~OnSideStream() { c->stream = main; }
   OnSideStream(const OnSideStream&) = delete;
   OnSideStream& operator=(const OnSideStream&) = delete;
+};
+// On any early exit the streams a call queued work on are drained before the host memory its copies land
+// in goes away (a pinned block on its way back to the pool, a local vector).  Declare it after that
+// memory, so it runs first; disarm it after the synchronisation that ends the call's device work.
+struct DrainOnExit {
+  sonar_ctx* c;
+  bool copy = false, side = false;   // this call also used c->copy / c->side
+  bool armed = true;
+  ~DrainOnExit() {
+    if (!armed) return;
+    if (copy) (void)hipStreamSynchronize(c->copy);
+    if (side) (void)hipStreamSynchronize(c->side);
+    (void)hipStreamSynchronize(c->stream);
+  }
 };
 }  // namespace detail
 }  // namespace sonar

@@ -507,5 +507,258 @@ bool detect_speech(int64_t n_samples, int rate, double crossings, double sum_sq,
   return check_periodicity(head, head_n);
 }
 
+// ---- MusicFeatureExtractor.ExtractFeatures' scalar tail (fingerprint/extractors/music.go) ----------
+
+int64_t go_int(double x) {
+  if (!(x >= -9.2233720368547758e18 && x < 9.2233720368547758e18)) return std::numeric_limits<int64_t>::min();
+  return (int64_t)x;
+}
+
+std::vector<int> contrast_edges(int sample_rate, int K, int nb) {
+  std::vector<int> e(nb + 1);
+  const double nyquist = (double)sample_rate / 2.0;
+  const double minf = 200.0;
+  double maxf = nyquist;
+  if (maxf <= minf) maxf = minf * 2;
+  const double lmin = std::log10(minf), lmax = std::log10(maxf);
+  const double step = (lmax - lmin) / (double)nb;
+  for (int i = 0; i <= nb; i++) {
+    const double f = std::pow(10.0, lmin + (double)i * step);
+    int64_t b = go_int(f * (double)(K - 1) / nyquist);
+    if (b >= K) b = K - 1;
+    if (b < 0) b = 0;
+    e[i] = (int)b;
+  }
+  for (int i = 1; i <= nb; i++)
+    if (e[i] <= e[i - 1]) e[i] = e[i - 1] + 1;
+  return e;
+}
+
+double gonum_variance(const double* x, size_t n) {                // common/math.go:22-27
+  if (n < 2) return 0.0;
+  double s = 0.0;
+  for (size_t i = 0; i < n; i++) s += x[i];
+  const double mean = s / (double)n;
+  double ss = 0.0, comp = 0.0;
+  for (size_t i = 0; i < n; i++) { const double d = x[i] - mean; ss += d * d; comp += d; }
+  return (ss - comp * comp / (double)n) / (double)(n - 1);
+}
+
+std::vector<double> crest_factors(const double* peaks, const double* energy, size_t n) {   // :428-444
+  std::vector<double> crest(n, 0.0);
+  for (size_t i = 0; i < n; i++) if (energy[i] > 0) crest[i] = peaks[i] / energy[i];
+  return crest;
+}
+
+std::vector<double> energy_entropy(const double* e, size_t n, double* loudness_range) {     // :481-510
+  std::vector<double> ent(n, 0.0);
+  double mx = 0.0, mn = std::numeric_limits<double>::infinity();
+  for (size_t i = 0; i < n; i++) {
+    if (e[i] > 0) ent[i] = -e[i] * std::log2(e[i]);
+    if (e[i] > mx) mx = e[i];
+    if (e[i] < mn && e[i] > 0) mn = e[i];
+  }
+  *loudness_range = (mn != std::numeric_limits<double>::infinity() && mn > 0) ? 20 * std::log10(mx / mn) : 0.0;
+  return ent;
+}
+
+bool chroma_slice_panics(int64_t F, int64_t hop, int64_t n, int64_t* frame) {
+  if (!((F - 1) * hop > n)) return false;
+  *frame = n / hop + 1;
+  return true;
+}
+
+bool percentile_panics(int64_t n, int64_t* index, int64_t* L) {
+  *L = n >= 1024 ? (n - 1024) / 512 + 1 : 0;
+  if (*L < 2) return false;
+  *index = go_int(10.0 * (double)(*L - 1));
+  return true;
+}
+
+// ---- ContentDetector (fingerprint/content_detector.go) ---------------------------------------------
+
+sonar_acoustic_features content_features(uint64_t crossings, double max, double min, const double* spec, int K,
+                                         const double* es, int64_t fe, const double* tsm, int64_t ft, int64_t n,
+                                         int sr) {
+  sonar_acoustic_features f = {};
+  // calculateZeroCrossingRate (:220-233)
+  f.zero_crossing_rate = n <= 1 ? 0.0 : (double)crossings / (double)(n - 1);
+  // calculateSpectralCentroid (:236-252)
+  {
+    double ws = 0.0, ms = 0.0;
+    for (int i = 0; i < K; i++) {
+      const double fr = (double)i * (double)sr / (double)(K * 2);
+      ws += fr * spec[i];
+      ms += spec[i];
+    }
+    f.spectral_centroid = ms == 0 ? 0.0 : ws / ms;
+  }
+  // calculateEnergyVariance (:255-290)
+  if (n >= 2048 && fe > 1) {
+    double mean = 0.0;
+    for (int64_t i = 0; i < fe; i++) mean += es[i] / 1024.0;
+    mean /= (double)fe;
+    double var = 0.0;
+    for (int64_t i = 0; i < fe; i++) {
+      const double d = es[i] / 1024.0 - mean;
+      var += d * d;
+    }
+    f.energy_variance = var / (double)fe;
+  }
+  // calculateSilenceRatio (:293-317)
+  if (fe > 0) {
+    int64_t silent = 0;
+    for (int64_t i = 0; i < fe; i++) silent += std::sqrt(es[i] / 1024.0) < 0.01;
+    f.silence_ratio = (double)silent / (double)fe;
+  }
+  // calculateDynamicRange (:320-343)
+  f.dynamic_range = (min == 0 || std::isinf(min)) ? 0.0 : 20.0 * std::log10(max / min);
+  // calculateFreqEnergyRatio (:346-369)
+  {
+    const int split = K / 4;
+    double lo = 0.0, hi = 0.0;
+    for (int i = 0; i < split && i < K; i++) lo += spec[i] * spec[i];
+    for (int i = split; i < K; i++) hi += spec[i] * spec[i];
+    const double tot = lo + hi;
+    if (tot != 0) { f.low_freq_energy = lo / tot; f.high_freq_energy = hi / tot; }
+  }
+  // calculateHarmonicRatio (:372-401)
+  if (K >= 10) {
+    std::vector<int> peaks;
+    for (int i = 2; i < K - 2; i++)
+      if (spec[i] > spec[i - 1] && spec[i] > spec[i + 1] && spec[i] > spec[i - 2] && spec[i] > spec[i + 2])
+        peaks.push_back(i);
+    if (peaks.size() >= 2) {
+      int harm = 0;
+      for (size_t q = 1; q < peaks.size(); q++) {
+        const double r = (double)peaks[q] / (double)peaks[0];
+        if (std::fabs(r - std::round(r)) < 0.1) harm++;
+      }
+      f.harmonic_ratio = (double)harm / (double)(peaks.size() - 1);
+    }
+  }
+  // calculateTemporalStability (:404-447)
+  const int64_t ts = sr / 10;
+  if (n >= 3 * ts && ft > 1) {
+    double mean = 0.0;
+    for (int64_t i = 0; i < ft; i++) mean += tsm[i];
+    mean /= (double)ft;
+    if (mean != 0) {
+      double var = 0.0;
+      for (int64_t i = 0; i < ft; i++) {
+        const double d = tsm[i] - mean;
+        var += d * d;
+      }
+      var /= (double)ft;
+      f.temporal_stability = go_max(0.0, 1.0 - std::sqrt(var) / mean);
+    }
+  }
+  return f;
+}
+
+ContentClass classify_content(const sonar_acoustic_features& f, double thr) {
+  double music = 0.0, speech = 0.0, sports = 0.0;
+  if (f.zero_crossing_rate < 0.1) music += 2.0;
+  if (f.harmonic_ratio > 0.3) music += 2.0;
+  if (f.temporal_stability > 0.5) music += 1.0;
+  if (f.dynamic_range > 20) music += 1.0;
+  if (f.zero_crossing_rate > 0.05 && f.zero_crossing_rate < 0.3) speech += 2.0;
+  if (f.spectral_centroid > 800 && f.spectral_centroid < 3000) speech += 2.0;
+  if (f.harmonic_ratio < 0.2) speech += 1.0;
+  if (f.silence_ratio > 0.1 && f.silence_ratio < 0.4) speech += 1.0;
+  if (f.energy_variance > 0.3) sports += 2.0;
+  if (f.dynamic_range > 30) sports += 1.5;
+  if (f.temporal_stability < 0.4) sports += 1.0;
+  const int types[4] = {SONAR_CT_MUSIC, SONAR_CT_NEWS, SONAR_CT_TALK, SONAR_CT_SPORTS};
+  const double scores[4] = {music, speech, speech * 0.9, sports};
+  ContentClass best = {SONAR_CT_UNKNOWN, 0.0};
+  double bs = thr;
+  for (int i = 0; i < 4; i++)
+    if (scores[i] > bs) { bs = scores[i]; best.type = types[i]; }
+  best.confidence = bs / 6.0;
+  return best;
+}
+
+// ---- VoiceQualityAnalyzer.AnalyzeVoiceQuality (algorithms/speech/voice_quality.go) -----------------
+
+PitchPeriods period_walk(const double* raw_pitch, const double* raw_conf, int64_t Fv, int64_t n, int sr) {
+  PitchPeriods w;
+  YinTracker tr;
+  int64_t last_end = 0;
+  for (int64_t i = 0; i < Fv; i++) {
+    double p = raw_pitch[i], cf = raw_conf[i], v = 0.0;
+    tr.step(p, cf, v);
+    if (v > 0.5 && cf > 0.5 && p >= 50.0 && p <= 500.0) {
+      const int64_t len = (int64_t)((double)sr / p);
+      const int64_t s0 = std::max<int64_t>(i * 256, last_end), e0 = s0 + len;
+      if (e0 < n) { w.st.push_back(s0); w.ln.push_back(len); w.f0.push_back(p); last_end = e0; }
+    }
+  }
+  if (n == 1024) { double p = raw_pitch[0], cf = raw_conf[0]; tr.step(p, cf, w.voicing); }
+  return w;
+}
+
+sonar_voice_quality_result voice_quality_from(const int64_t* ln, const double* amp, const double* f0, int64_t np,
+                                              const double* ac, const double* head, int64_t n, int sr, double vstr) {
+  // calculateJitter (:160-191) and calculateShimmer (:194-229)
+  double avg = 0.0, js = 0.0;
+  for (int64_t k = 0; k < np; k++) avg += (double)ln[k];
+  avg /= (double)np;
+  for (int64_t k = 1; k < np; k++) js += std::fabs((double)ln[k] - (double)ln[k - 1]);
+  const double jitter = avg == 0 ? 0.0 : (js / (double)(np - 1)) / avg * 100.0;
+  double aavg = 0.0, ss = 0.0;
+  for (int64_t k = 0; k < np; k++) aavg += amp[k];
+  aavg /= (double)np;
+  for (int64_t k = 1; k < np; k++) ss += std::fabs(amp[k] - amp[k - 1]);
+  const double shimmer = aavg == 0 ? 0.0 : (ss / (double)(np - 1)) / aavg * 100.0;
+  // calculateHNR (:232-294): peak of the autocorrelation within +-25 % of the mean-F0 lag
+  double mf = 0.0, hnr = 0.0;
+  for (int64_t k = 0; k < np; k++) mf += f0[k];
+  mf /= (double)np;
+  if (ac) {
+    const int64_t el = (int64_t)((double)sr / mf);
+    if (el < 2048) {
+      const int64_t r = el / 4, a = std::max<int64_t>(1, el - r), b = std::min<int64_t>(2047, el + r);
+      double mc = 0.0;
+      for (int64_t i = a; i <= b; i++) if (ac[i] > mc) mc = ac[i];
+      if (mc > 0 && mc < ac[0]) hnr = 10.0 * std::log10(mc / (ac[0] - mc));
+    }
+  }
+  // calculateF0Stability (:297-322), calculateAmplitudeStability (:325-360)
+  double var = 0.0;
+  for (int64_t k = 0; k < np; k++) { const double d = f0[k] - mf; var += d * d; }
+  var /= (double)np;
+  const double f0s = mf == 0 ? 0.0 : go_max(0.0, 1.0 - std::sqrt(var) / mf);
+  double av = 0.0;
+  for (int64_t k = 0; k < np; k++) { const double d = amp[k] - aavg; av += d * d; }
+  av /= (double)np;
+  const double ams = aavg == 0 ? 0.0 : go_max(0.0, 1.0 - std::sqrt(av) / aavg);
+  // calculateNoiseMeasure (:374-398) on the first 1024 samples
+  double nm = 0.0;
+  if (n >= 1024) {
+    double hf = 0.0, te = 0.0;
+    for (int i = 1; i < 1024; i++) { const double d = head[i] - head[i - 1]; hf += d * d; te += head[i] * head[i]; }
+    nm = te == 0 ? 0.0 : hf / te;
+  }
+  // calculateF0Statistics (:401-426), calculateOverallQuality (:429-437), calculateAnalysisQuality (:440-451)
+  double lo = f0[0], hi = f0[0];
+  for (int64_t k = 0; k < np; k++) { if (f0[k] < lo) lo = f0[k]; if (f0[k] > hi) hi = f0[k]; }
+  sonar_voice_quality_result q = {};
+  q.jitter = jitter;
+  q.shimmer = shimmer;
+  q.hnr = hnr;
+  q.noise_measure = nm;
+  q.f0_stability = f0s;
+  q.amplitude_stability = ams;
+  q.voicing_strength = vstr;
+  q.overall_quality = (go_max(0, 1.0 - jitter / 5.0) + go_max(0, 1.0 - shimmer / 10.0) +
+                       go_min(1.0, go_max(0, hnr / 20.0)) + f0s) / 4.0;
+  q.num_periods = np;
+  q.mean_f0 = mf;
+  q.f0_range = hi - lo;
+  q.analysis_quality = (go_min(1.0, (double)np / 10.0) + f0s + go_min(1.0, go_max(0, hnr / 15.0))) / 3.0;
+  return q;
+}
+
 }  // namespace host
 }  // namespace sonar

@@ -4,6 +4,9 @@
 // extractor's tail, NCC peak metrics, alignment scorers).  Pure C++17, float64,
 // Go evaluation order.
 #pragma once
+#include "../../include/sonar_gpu.h"
+
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -109,6 +112,51 @@ AlignScores dtw_scores(const PathSums& s, int64_t nq, int64_t nr, double distanc
 double energy_variance(const double* e, size_t n);
 // ComputeLoudnessRange tail: RMS of 400 ms / 100 ms frames -> LU -> 10th..95th percentile range
 double loudness_range_from_rms(std::vector<double> rms);
+
+// MusicFeatureExtractor.ExtractFeatures' scalar tail (fingerprint/extractors/music.go:378-525)
+// Go int(float64) on amd64 (CVTTSD2SQ): NaN / out of range -> MinInt64
+int64_t go_int(double x);
+// SpectralContrast.initializeBands (spectral_contrast.go:140-185): nb + 1 bin edges
+std::vector<int> contrast_edges(int sample_rate, int K, int nb);
+// gonum stat.Variance(x, nil) (v0.16.0 MeanVariance: compensated two-pass, n - 1), with the
+// mean's sum sequential (gonum's amd64 kernel pairs terms: agreement to rounding, parity unpinned)
+double gonum_variance(const double* x, size_t n);
+std::vector<double> crest_factors(const double* peaks, const double* energy, size_t n);      // :428-444
+// -e log2 e per frame (:481-497), and 20 log10 of the largest over the smallest positive energy (:499-510)
+std::vector<double> energy_entropy(const double* e, size_t n, double* loudness_range);
+// Where Go panics, and what its runtime message names.  extractChromaFeatures slices
+// processedPCM[f hop : min(f hop + n / F, n)] (:348-352, hop > 0): with (F - 1) hop > n the first frame
+// starting past the end is *frame, "slice bounds out of range [*frame hop:n]".
+bool chroma_slice_panics(int64_t F, int64_t hop, int64_t n, int64_t* frame);
+// DynamicRange.ComputeRange(pcm, 10, 90) (:401-403, dynamic_range.go:58-76) reads sorted[int(10 (L - 1))] of
+// the L RMS frames 1024 / 512: "index out of range [*index] with length *L" for every L >= 2
+bool percentile_panics(int64_t n, int64_t* index, int64_t* L);
+
+// ContentDetector.extractAcousticFeatures (fingerprint/content_detector.go:118-150) from the whole signal's
+// sign changes and extrema of |x|, the K magnitudes of its first 2 (K - 1) samples' DFT, the fe sums of
+// squares of frames 1024 / 512 and the ft of frames of 100 ms; classification_confidence is left 0
+sonar_acoustic_features content_features(uint64_t crossings, double max, double min, const double* spec, int K,
+                                         const double* esum, int64_t fe, const double* tsum, int64_t ft, int64_t n,
+                                         int sr);
+// classifyFromFeatures (:153-217): the first score strictly above thr and the others (Go iterates a map;
+// here music, news, talk, sports); confidence = the winning score, or thr, over 6
+struct ContentClass { int type; double confidence; };
+ContentClass classify_content(const sonar_acoustic_features& f, double thr);
+
+// VoiceQualityAnalyzer.extractPitchPeriodsAndF0 (algorithms/speech/voice_quality.go:114-157) over the raw
+// YIN rows of the Fv frames 1024 / 256 of an n-sample signal: a fresh PitchDetector, voiced frames with
+// voicing and confidence > 0.5 and F0 in [50, 500]; each period starts at max(frame start, last end).
+// voicing: calculateVoicingStrength (:363-371), which DetectPitch answers only for n == 1024 (row 0 again).
+struct PitchPeriods {
+  std::vector<int64_t> st, ln;
+  std::vector<double> f0;
+  double voicing = 0.0;
+};
+PitchPeriods period_walk(const double* raw_pitch, const double* raw_conf, int64_t Fv, int64_t n, int sr);
+// The scalar formulas (:160-451) over np >= 3 periods: their lengths, RMS amplitudes and F0, the 2048-lag
+// autocorrelation of the middle frame (null for n < 2048) and the first min(n, 1024) samples
+sonar_voice_quality_result voice_quality_from(const int64_t* ln, const double* amp, const double* f0, int64_t np,
+                                              const double* ac, const double* head, int64_t n, int sr, double vstr);
 
 }  // namespace host
 }  // namespace sonar

@@ -796,7 +796,8 @@ int launch_dc_preemph(const double* x, int64_t n, double R, double alpha, double
 // MusicFeatureExtractor energy + chroma of many signals in five launches (jobs on the device in
 // djobs, the same on the host in hjobs for the grid sizes): DC removal + pre-emphasis (the same
 // three passes as launch_dc_preemph), ShortTimeEnergy of the pre-emphasised signal (alpha 0, as
-// music_features_impl), chroma (chroma_wave_kernel, fs 256 or 512; tables shared by every job).
+// music_api.cpp's music_features_impl), chroma (chroma_wave_kernel, fs 256 or 512; tables shared by
+// every job).
 // Returns -1 without launching when a job does not fit those kernels (the caller then runs the
 // per-signal path).
 int launch_music_features_batch(const MfJob* hjobs, const MfJob* djobs, int nj, int W, int H, int fs,

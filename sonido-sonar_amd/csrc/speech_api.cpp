@@ -82,21 +82,6 @@ struct SpeechRun {
   size_t cnt(SpeechPlan::Section s) const { return p.sec[s].cnt; }
 };
 
-// On any early exit the streams this call queued work on are drained before the pinned block goes back
-// to the process-wide pool: copies into it are queued on c->stream, and with the early tracker YIN writes
-// into it on the side stream.  Declared after the block, so it runs first.
-struct DrainOnExit {
-  sonar_ctx* c;
-  bool copy;                       // this call used c->copy
-  bool armed = true;
-  ~DrainOnExit() {
-    if (!armed) return;
-    if (copy) (void)hipStreamSynchronize(c->copy);
-    (void)hipStreamSynchronize(c->side);
-    (void)hipStreamSynchronize(c->stream);
-  }
-};
-
 int reserve(sonar_ctx* c, int64_t n, const SpeechPlan& p, SpeechBufs* b) {
   auto buf = [&](const char* name, int64_t doubles) {
     return (double*)dbuf(c, name, (size_t)std::max<int64_t>(doubles, 1) * 8);
@@ -509,7 +494,9 @@ int sonar_extract_speech_features(sonar_ctx* c, const double* pcm, int64_t n, in
       (void)hipGetLastError();
     }
   }
-  DrainOnExit drain{c, r.NCH > 1};
+  // copies into the block are queued on c->stream, and with the early tracker YIN writes into it on the
+  // side stream: an early exit drains them before the block goes back to the pool
+  sonar::detail::DrainOnExit drain{c, r.NCH > 1, true};
   std::unique_ptr<sonar_result> res(new sonar_result());
   res->hold(blk);
 

@@ -135,3 +135,18 @@ def test_generate_fingerprint_detects_unknown_content(ctx):
     for k in ("mfcc", "spectral_centroid", "short_time_energy"):
         if k in b:
             assert np.array_equal(a[k], b[k]), k
+
+
+def test_scratch_block_carve_shrinks_and_grows(ctx):
+    """One scratch block carved at a large, two small and the large size again on one context: every feature is
+    exactly that of the same call on a context that holds no scratch yet."""
+    sig = _signals()
+    for name in ("sweep10s", "n100", "n2048", "sweep10s"):
+        x, sr = sig[name]
+        fresh = Context(0)
+        want = fresh.detect_from_audio(x, sr)
+        fresh.close()
+        got = ctx.detect_from_audio(x, sr)
+        assert got[0] == want[0], name
+        for k, v in want[1].items():
+            assert got[1][k] == v or (np.isnan(v) and np.isnan(got[1][k])), (name, k, got[1][k], v)

@@ -151,3 +151,64 @@ def test_invalid_input(ctx):
     with pytest.raises(sonar.SonarError) as ei:
         ctx.extract_music_features(np.zeros(0), 44100, _fc(ctx)[0])
     assert "invalid input data" in ei.value.msg
+
+
+def test_live_harmonic_block_on_clean_tone(ctx):
+    """n == 1024 with both windows 1024: the one frame DetectPitch accepts (F7).  A clean 440 Hz tone stays
+    above the pre-emphasis, so the harmonic block is live: YIN through the first step of a fresh tracker."""
+    n = 1024
+    x = 0.5 * np.sin(2 * np.pi * 440.0 * np.arange(n) / 44100.0)
+    got, err, ref, panic = _run(ctx, x)
+    assert panic is None and err is None, (panic, err)
+    assert ref["voicing_strength"][0] > 0.5
+    assert ref["pitch_estimate"][0] > 0 and ref["tonal_centroid"][0] > 0
+    assert set(got) == set(ref), sorted(set(got) ^ set(ref))
+    _compare(got, ref)
+
+
+def _sweep_noise(seconds):
+    return synth.sweep(seconds) + 0.01 * np.random.default_rng(3).standard_normal(int(seconds * 44100))
+
+
+def _call(c, x, **kw):
+    """(result or partial result, (code, message) or None)"""
+    try:
+        return c.extract_music_features(x, 44100, _fc(c, **kw)[0]), None
+    except sonar.SonarError as e:
+        return e.partial, (e.code, e.msg)
+
+
+def _same_result(a, b):
+    assert list(a) == list(b)
+    for k in a:
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), k
+
+
+def test_scratch_reuse_equals_fresh_context(ctx):
+    """Large (panic regime, partial result), small, large again on one context: every result and error is that
+    of the same call on a context that holds no scratch yet."""
+    big = _sweep_noise(2.0)
+    t = np.arange(1300) / 44100.0
+    small = 0.5 * np.sin(2 * np.pi * 220.0 * t) + 0.05 * np.random.default_rng(1300 + 1024).standard_normal(1300)
+    skw = dict(stft_window_size=1024, stft_hop_size=256, window_size=512, hop_size=128)
+    want = []
+    for x, kw in ((big, {}), (small, skw)):
+        fresh = sonar.Context(0)
+        want.append(_call(fresh, x, **kw))
+        fresh.close()
+    assert want[0][1] is not None and want[0][1][0] == sonar.ERR_PANIC and want[1][1] is None
+    for (x, kw), (res, err) in zip(((big, {}), (small, skw), (big, {})), (want[0], want[1], want[0])):
+        got, gerr = _call(ctx, x, **kw)
+        assert gerr == err
+        _same_result(got, res)
+
+
+def test_extractor_and_alignment_features_share_preprocessing(ctx):
+    """preprocessAudio, ShortTimeEnergy and the chroma are one path for the extractor and for
+    sonar_music_alignment_features: the same launches with the same arguments."""
+    x = _sweep_noise(2.0)
+    got, err = _call(ctx, x)
+    assert err is not None and err[0] == sonar.ERR_PANIC
+    energy, chroma = ctx.music_alignment_features(x, 44100, 1024, 256, 1024, 256)
+    assert np.array_equal(np.ravel(got["rms_energy"]), energy)
+    assert np.array_equal(np.asarray(got["chroma"]).reshape(chroma.shape), chroma)

@@ -66,3 +66,33 @@ def test_speech_extractor_jitter_shimmer(ctx, prec):
     assert ref["jitter"] > 0 and ref["shimmer"] > 0
     assert got["jitter"] == pytest.approx(ref["jitter"], rel=1e-12)
     assert got["shimmer"] == pytest.approx(ref["shimmer"], rel=1e-12)
+
+
+def test_voice_quality_scratch_reuse_equals_fresh_context(ctx):
+    """4 s voiced, the 2 s tone, 4 s again on one context: each result is exactly a fresh context's."""
+    sr = 16000
+    t = np.arange(2 * sr) / sr
+    long_ = O.preemphasis(synth.voiced(seconds=4.0), 0.97)
+    tone = O.preemphasis(np.sin(2 * np.pi * 200 * t) + 0.3 * np.sin(2 * np.pi * 400 * t), 0.97)
+    want = []
+    for y in (long_, tone):
+        fresh = sonar.Context(0)
+        want.append(fresh.voice_quality(y, sr))
+        fresh.close()
+    for y, w in ((long_, want[0]), (tone, want[1]), (long_, want[0])):
+        got = ctx.voice_quality(y, sr)
+        assert list(got) == list(w)
+        for k in w:
+            assert got[k] == w[k] or (np.isnan(w[k]) and np.isnan(got[k])), k
+
+
+def test_insufficient_periods_message_names_the_count(ctx):
+    """The Go error text carries the number of periods found (voice_quality.go:67-69): the oracle's count."""
+    sr = 16000
+    x = np.random.default_rng(0).standard_normal(2 * sr)
+    ref, st = O.voice_quality(x, sr)
+    assert st == -2 and 0 <= ref["num_periods"] < 3
+    with pytest.raises(sonar.SonarError) as ei:
+        ctx.voice_quality(x, sr)
+    assert ei.value.code == sonar.ERR_TOO_SHORT
+    assert ei.value.msg == "insufficient pitch periods for analysis (found %d, need at least 3)" % ref["num_periods"]
