@@ -18,6 +18,10 @@
  *   sonar_fingerprint_batch    <- SpectralAnalyzer.ComputeSTFTBatch (fingerprint/analyzers/spectral.go:234)
  *   sonar_pitch_yin            <- PitchDetector.DetectPitch per-frame YIN core
  *                                 (algorithms/tonal/pitch_detection.go:225-420)
+ *   sonar_pitch_frames_raw, sonar_pitch_detect, sonar_pitch_track, sonar_pitch_stability
+ *                              <- PitchDetector.DetectPitch for every method of its switch,
+ *                                 ProcessAudioStream, postProcessResult + updateTemporalTracking,
+ *                                 AnalyzePitchStability (pitch_detection.go:225-1160)
  *   sonar_chroma_stft          <- MusicFeatureExtractor.extractChromaFeatures
  *                                 (fingerprint/extractors/music.go:327) ->
  *                                 ChromaSTFT.ComputeChroma (algorithms/chroma/chroma_stft.go:45)
@@ -1556,6 +1560,158 @@ int sonar_merge_matches(const sonar_match* const* lists, const int64_t* counts, 
 int sonar_find_best_matches_multi(sonar_multi* m, sonar_gallery* const* galleries, const int64_t* const* queries,
                                   int64_t nq, const int64_t* const* candidates, const int64_t* nc,
                                   const sonar_compare_cfg* cfg, sonar_match* out, int64_t* n_matches);
+
+/* ---- PitchDetector in full (algorithms/tonal/pitch_detection.go): every method of DetectPitch's
+ * switch (:239-260) at any supported window, threshold and frequency range, its post-processing and
+ * temporal tracking, ProcessAudioStream and AnalyzePitchStability.  sonar_pitch_yin above stays the
+ * constructor-default YIN core; at the defaults the YIN rows here are the same bits. ------------- */
+enum {                             /* PitchDetectionMethod (:16-35), Go's values */
+  SONAR_PITCH_YIN = 0,
+  SONAR_PITCH_ACF = 1,
+  SONAR_PITCH_NSDF = 2,
+  SONAR_PITCH_HPS = 3,
+  SONAR_PITCH_CEPSTRUM = 4,
+  SONAR_PITCH_PEAKS = 5,           /* detectPitchPeaks is detectPitchHPS (:687-691) */
+  SONAR_PITCH_ZERO_CROSSING = 6,
+  SONAR_PITCH_PEAK_PICKING = 7,    /* not in the switch: "unsupported pitch detection method: 7" */
+  SONAR_PITCH_YIN_FFT = 8,         /* detectPitchYinFFT is detectPitchYin (:730-733) */
+  SONAR_PITCH_MPM = 9,             /* detectPitchMPM is detectPitchNSDF (:736-740) */
+  SONAR_PITCH_PRAAT = 10           /* not in the switch */
+};
+enum {                             /* createWindowFunction's strings (:317-345); Go maps every other string to
+                                      Hann, which the bindings do before they fill the field */
+  SONAR_PITCH_WIN_HANN = 0,
+  SONAR_PITCH_WIN_HAMMING = 1,
+  SONAR_PITCH_WIN_BLACKMAN = 2,
+  SONAR_PITCH_WIN_RECTANGULAR = 3
+};
+/* PitchDetectionParams (:84-117) field for field.  The reference never reads cepstral_threshold,
+ * min_salience, voicing_threshold, max_harmonics and harmonic_tolerance; hop_size is read only by
+ * estimateVibratoRate (:1156) -- the entries here also use it as the frame step of a signal, which in Go
+ * is the caller's slicing.  The library ignores the never-read fields as well. */
+typedef struct sonar_pitch_params {
+  int32_t method;                  /* SONAR_PITCH_* */
+  int32_t sample_rate;
+  int32_t window_size;
+  int32_t hop_size;
+  double min_freq, max_freq;
+  double yin_threshold;
+  double autocorr_threshold;       /* ACF and NSDF peaks; see the un-normalised ACF below */
+  double cepstral_threshold;       /* never read */
+  double min_confidence;
+  double min_salience;             /* never read */
+  double voicing_threshold;        /* never read */
+  int32_t max_harmonics;           /* never read */
+  double harmonic_tolerance;       /* never read */
+  int32_t pre_emphasis;            /* 0 / 1: y[i] = x[i] - 0.97 x[i - 1], fresh per frame (:300-314) */
+  int32_t window_function;         /* SONAR_PITCH_WIN_*, denominator W - 1 */
+  int32_t zero_padding;            /* HPS / PEAKS: the transform has W * zero_padding points */
+  int32_t median_filter;
+  int32_t temporal_smoothing;      /* 0 / 1 */
+  int32_t octave_correction;       /* 0 / 1 */
+} sonar_pitch_params;
+
+/* NewPitchDetector(sample_rate) (:159-193): YIN, 1024 / 512, 80-1000 Hz, 0.15, 0.3, 0.3, 0.5, 0.1, 0.45,
+ * 10, 0.1, pre-emphasis, Hann, zero padding 2, median 3, smoothing and octave correction on. */
+void sonar_pitch_params_default(sonar_pitch_params* p, int32_t sample_rate);
+
+/* n < W ? 0 : (n - W) / H + 1 whole frames of W samples every H: DetectPitch rejects a frame of any
+ * other length (:226), so a trailing partial frame does not count.  W < 1 or H < 1 gives 0. */
+int64_t sonar_pitch_detect_frames(int64_t n, int32_t window_size, int32_t hop_size);
+
+/* The parameter checks of the entries below, without a device, and the width of a frame's curve:
+ * YIN / YIN_FFT the CMNDF, W / 2; NSDF / MPM the NSDF, W / 2; ACF the correlations (AutocorrPeaks,
+ * lags -(W - 1) .. W - 1), 2 W - 1; HPS / PEAKS the harmonic product, W * zero_padding / 2; cepstrum the
+ * real cepstrum, W; zero crossing none, 0.  Returns the width or a negative SONAR_ERR_*:
+ *   PEAK_PICKING, PRAAT and unknown methods -> SONAR_ERR_INVALID "unsupported pitch detection method: N"
+ *     (:259), before anything else is looked at;
+ *   hop_size < 1 or sample_rate < 1 -> SONAR_ERR_INVALID;
+ *   not 0 < min_freq < max_freq, both finite -> SONAR_ERR_INVALID (a documented narrowing: Go would
+ *     divide by zero or convert an infinity to int);
+ *   HPS / PEAKS with zero_padding < 1 -> SONAR_ERR_PANIC (hps[0] of an empty slice, :580);
+ *   cepstrum with int(sample_rate / max_freq) >= W -> SONAR_ERR_PANIC (:650);
+ *   window_size not a power of two in [64, 2048], or HPS / PEAKS with zero_padding not 1, 2 or 4 or
+ *     W * zero_padding > 4096, or a window_function outside the enum -> SONAR_ERR_UNSUPPORTED (the
+ *     largest transform, the ACF's 2 W included, fits one 4096-point LDS tile). */
+int64_t sonar_pitch_curve_width(const sonar_pitch_params* p);
+
+/* DetectPitch up to postProcessResult, per frame f of pcm (float64, n samples; host pointers, or
+ * device pointers for pcm and every output when device_ptrs is set): preprocessFrame (:282-345), then
+ * the method.  Outputs, F = sonar_pitch_detect_frames(n, W, H) entries each unless noted; all but pitch
+ * and confidence may be NULL:
+ *   pitch, confidence   what detectPitch* returns (Periodicity and Voicing equal confidence)
+ *   index               the chosen lag (YIN: minTau, also when its frequency is out of range; ACF, NSDF),
+ *                       bin (HPS), quefrency (cepstrum) or the crossing count; -1 when none
+ *   n_candidates        len(Candidates), all of them, not only the reported ones
+ *   second_confidence   Candidates[1].Confidence for calculateClarity (:840), 0 with fewer than two
+ *   cand_index, cand_conf   F x max_candidates (0..8): the best candidates by descending confidence;
+ *                       unused slots are -1 and 0
+ *   curve               F x sonar_pitch_curve_width(p)
+ * Quirks of the reference kept here:
+ *  - YIN / YIN_FFT (:349-420): halfN = W / 2, the first tau with cmndf < yin_threshold that is below its
+ *    right neighbour, parabolic interpolation, the frequency gate; bit-identical to a sequential float64
+ *    evaluation in Go's order (and to sonar_pitch_yin at the defaults).
+ *  - NSDF / MPM (:485-550): acf, m1 and m2 are three sums in j order; peaks are strict local maxima above
+ *    autocorr_threshold at 1 <= i <= W/2 - 2 with sample_rate / i in range.  Bit-identical.
+ *  - ACF (:423-482): AutoCorrelation.Compute on the preprocessed frame exactly as sonar_autocorr defines
+ *    it with max_lag 2 W, i.e. use_fft is set and the regime depends on W: W > 1000 is the
+ *    frequency-domain regime, z-score, N = 2 W, re(ifft(fft conj(fft))) / N and NOT normalised further, so
+ *    autocorr_threshold compares values of the order of W (lag 0 is W); W <= 512 is Pearson per lag in
+ *    [-1, 1].  Candidates are lags 1 .. W - 2.  Bit-identical to sonar_autocorr on the same frame.
+ *  - Candidate order: Go's sort.Slice is not stable, so the reference leaves the order of equal
+ *    confidences unspecified; the library orders them by ascending lag.
+ *  - HPS / PEAKS (:553-620): zero-padded to W * zero_padding, |X| of the first half, times the harmonics
+ *    2..5 over len / h bins; the scan over [int(min_freq N / sr), int(max_freq N / sr)) clipped to the
+ *    length starts from maxIdx = 0, maxVal = hps[0] with a strict >, so when nothing beats bin 0 the pitch
+ *    is 0 Hz and a confidence min(maxVal / 1000, 1) is still reported.  The transform is go-dsp's in the
+ *    reference: parity at tolerance.
+ *  - Cepstrum (:623-684): ln(|X| + 1e-10) of the W-point spectrum, the inverse transform's real part, the
+ *    scan from int(sr / max_freq) to min(int(sr / min_freq), W) with a strict >, pitch sr / index,
+ *    confidence min(max / 0.1, 1), which may be negative.  Parity at tolerance.
+ *  - Zero crossing (:694-727): crossings of the preprocessed frame, pitch crossings sr / (2 W),
+ *    confidence 0.3 (which the default min_confidence gate zeroes).
+ * Errors: those of sonar_pitch_curve_width; max_candidates outside 0..8, n < 0, NULL pcm with frames
+ * due, NULL pitch or confidence -> SONAR_ERR_INVALID.  F == 0 succeeds and writes nothing. */
+int sonar_pitch_frames_raw(sonar_ctx* ctx, const double* pcm, int64_t n, const sonar_pitch_params* p,
+                           int32_t max_candidates, double* pitch, double* confidence, int32_t* index,
+                           int32_t* n_candidates, double* second_confidence, int32_t* cand_index,
+                           double* cand_conf, double* curve, int32_t device_ptrs);
+
+/* postProcessResult + updateTemporalTracking (:767-963) over F raw rows in order, from an empty history
+ * (a fresh detector, or one after Reset).  Host-only, no context.  Per frame:
+ *  - octave correction (octave_correction) of a non-zero pitch against the median of the positive ones
+ *    among the last five history entries, once three entries exist: ratios 0.5, 2, 1/3, 3 in that order,
+ *    the first within 10 % decides, and the pitch moves to median * ratio (f0_multiple = ratio) only when
+ *    that is closer to the median; f0_multiple is 0 otherwise;
+ *  - clarity (:830-849), strength and salience (:852-873) are computed BEFORE the min_confidence gate;
+ *  - the gate (:783-787) zeroes pitch, confidence and voicing but not periodicity;
+ *  - the history holds the last 20 gated, octave-corrected and UNSMOOTHED pitches; stability
+ *    (calculateStability :924-963) runs over it;
+ *  - smoothing (temporal_smoothing, from the second frame): the median of the positive entries among the
+ *    last median_filter ones when at least three exist (median_filter above 20 reads the whole history,
+ *    below 1 none), otherwise 0.3 p + 0.7 previous, previous being the last smoothed pitch.
+ * Reads octave_correction, temporal_smoothing, median_filter and min_confidence of p.  n_candidates and
+ * second_confidence may be NULL (one candidate whenever the raw confidence is not 0).  Every output may
+ * be NULL. */
+int sonar_pitch_track(const sonar_pitch_params* p, int64_t F, const double* raw_pitch,
+                      const double* raw_confidence, const int32_t* n_candidates, const double* second_confidence,
+                      double* pitch, double* confidence, double* voicing, double* periodicity, double* clarity,
+                      double* strength, double* salience, double* stability, double* f0_multiple);
+
+/* ProcessAudioStream (:1016-1028) over the frames of pcm: sonar_pitch_frames_raw, then
+ * sonar_pitch_track, in one call.  With device_ptrs, pcm and the nine outputs are device pointers. */
+int sonar_pitch_detect(sonar_ctx* ctx, const double* pcm, int64_t n, const sonar_pitch_params* p, double* pitch,
+                       double* confidence, double* voicing, double* periodicity, double* clarity, double* strength,
+                       double* salience, double* stability, double* f0_multiple, int64_t* frames,
+                       int32_t device_ptrs);
+
+/* AnalyzePitchStability + estimateVibratoRate (:1059-1160) of a pitch sequence.  Host-only.  out7:
+ * mean_pitch, pitch_std_dev, coefficient_of_variation, jitter, stability, vibrato_rate,
+ * voiced_frames_ratio; *empty = 1 and zeros for the empty map Go returns with fewer than two entries or
+ * fewer than two voiced (> 0) ones.  The vibrato rate is 0 below ten voiced frames and reads
+ * sample_rate / hop_size. */
+int sonar_pitch_stability(const double* pitch, int64_t n, int32_t sample_rate, int32_t hop_size, double* out7,
+                          int32_t* empty);
 
 /* result accessors: rows*cols float64 values, row-major; scalars are 1x1 */
 int sonar_result_get(const sonar_result* res, const char* name, const double** data, int64_t* rows,

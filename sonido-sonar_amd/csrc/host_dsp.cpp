@@ -760,5 +760,112 @@ sonar_voice_quality_result voice_quality_from(const int64_t* ln, const double* a
   return q;
 }
 
+// ---- PitchDetector post-processing for every method and parameter set (pitch_detection.go:767-1160)
+static double median_positive_n(const double* v, int n) {        // calculateMedian :978-1007, n <= 20
+  double tmp[20];
+  int m = 0;
+  for (int i = 0; i < n; i++)
+    if (v[i] > 0) {
+      int j = m++;
+      while (j > 0 && tmp[j - 1] > v[i]) { tmp[j] = tmp[j - 1]; --j; }
+      tmp[j] = v[i];
+    }
+  if (m == 0) return 0.0;
+  return (m % 2 == 0) ? (tmp[m / 2 - 1] + tmp[m / 2]) / 2.0 : tmp[m / 2];
+}
+
+PitchRow PitchTracker::step(const PitchTrackParams& prm, double raw_pitch, double raw_conf, int n_candidates,
+                            double second_conf) {
+  PitchRow r;
+  r.pitch = raw_pitch; r.confidence = raw_conf; r.voicing = raw_conf; r.periodicity = raw_conf;
+  if (prm.octave_correction && r.pitch != 0.0 && count > 0) {     // applyOctaveCorrection :793-827
+    const int cnt = std::min(count, 5);
+    if (cnt >= 3) {
+      const double med = median_positive_n(hist + count - cnt, cnt);
+      const double ratios[4] = {0.5, 2.0, 1.0 / 3.0, 3.0};
+      for (double q : ratios) {
+        const double ex = med * q;
+        if (std::fabs(r.pitch - ex) / ex < 0.1) {
+          if (std::fabs(r.pitch - med) > std::fabs(ex - med)) { r.pitch = ex; r.f0_multiple = q; }
+          break;
+        }
+      }
+    }
+  }
+  if (n_candidates == 1) r.clarity = raw_conf;                     // calculateClarity :830-849
+  else if (n_candidates > 1 && raw_conf > 0) r.clarity = (raw_conf - second_conf) / raw_conf;
+  r.strength = (r.periodicity + r.voicing) / 2.0;                  // calculateStrength :852-855
+  double base = r.confidence;                                      // calculateSalience :858-873
+  if (r.pitch >= 200 && r.pitch <= 800) base *= 1.2;
+  if (r.pitch < 100 || r.pitch > 1000) base *= 0.8;
+  r.salience = go_min(base, 1.0);
+  if (r.confidence < prm.min_confidence) { r.pitch = 0.0; r.confidence = 0.0; r.voicing = 0.0; }   // :783-787
+  if (count == 20) {                                               // updateTemporalTracking :876-902
+    for (int i = 1; i < 20; i++) hist[i - 1] = hist[i];
+    hist[19] = r.pitch;
+  } else {
+    hist[count++] = r.pitch;
+  }
+  if (prm.temporal_smoothing && count > 1) {                       // applyTemporalSmoothing :905-921
+    const int cnt = prm.median_filter > 0 ? std::min(count, prm.median_filter) : 0;
+    if (cnt >= 3) r.pitch = median_positive_n(hist + count - cnt, cnt);
+    else r.pitch = 0.3 * r.pitch + (1 - 0.3) * prev;
+  }
+  if (count >= 3) {                                                // calculateStability :924-963
+    int m = 0;
+    double mean = 0.0;
+    for (int i = 0; i < count; i++) if (hist[i] > 0) { mean += hist[i]; ++m; }
+    if (m >= 2) {
+      mean /= (double)m;
+      double var = 0.0;
+      for (int i = 0; i < count; i++) if (hist[i] > 0) { const double d = hist[i] - mean; var += d * d; }
+      var /= (double)(m - 1);
+      if (mean > 0) r.stability = go_max(0.0, 1.0 - std::sqrt(var) / mean);
+    }
+  }
+  prev = r.pitch;
+  return r;
+}
+
+bool pitch_stability(const double* pitch, int64_t n, int sample_rate, int hop_size, double out7[7]) {
+  for (int k = 0; k < 7; k++) out7[k] = 0.0;
+  if (n < 2) return false;
+  std::vector<double> v;
+  for (int64_t i = 0; i < n; i++) if (pitch[i] > 0) v.push_back(pitch[i]);
+  const size_t m = v.size();
+  if (m < 2) return false;
+  double mean = 0.0;
+  for (double x : v) mean += x;
+  mean /= (double)m;
+  double var = 0.0;
+  for (double x : v) { const double d = x - mean; var += d * d; }
+  var /= (double)(m - 1);
+  const double sd = std::sqrt(var);
+  double jitter = 0.0;
+  for (size_t i = 1; i < m; i++) jitter += std::fabs(v[i] - v[i - 1]);
+  jitter /= (double)(m - 1);
+  double vib = 0.0;                                                // estimateVibratoRate :1116-1160
+  if (m >= 10) {
+    const double nn = (double)m;
+    const double sx = nn * (nn - 1) / 2, sx2 = (nn - 1) * nn * (2 * nn - 1) / 6;
+    double sy = 0.0, sxy = 0.0;
+    for (size_t i = 0; i < m; i++) { sy += v[i]; sxy += (double)i * v[i]; }
+    const double slope = (nn * sxy - sx * sy) / (nn * sx2 - sx * sx);
+    const double icpt = (sy - slope * sx) / nn;
+    int64_t cross = 0;
+    double prevd = 0.0;
+    for (size_t i = 0; i < m; i++) {
+      const double d = v[i] - (icpt + slope * (double)i);
+      if (i > 0 && ((d > 0 && prevd <= 0) || (d <= 0 && prevd > 0))) ++cross;
+      prevd = d;
+    }
+    const double hop_rate = (double)sample_rate / (double)hop_size;
+    vib = (double)cross / (2.0 * nn / hop_rate);
+  }
+  out7[0] = mean; out7[1] = sd; out7[2] = sd / mean; out7[3] = jitter;
+  out7[4] = 1.0 / (1.0 + sd / mean); out7[5] = vib; out7[6] = (double)m / (double)n;
+  return true;
+}
+
 }  // namespace host
 }  // namespace sonar

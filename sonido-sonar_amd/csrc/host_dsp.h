@@ -158,5 +158,31 @@ PitchPeriods period_walk(const double* raw_pitch, const double* raw_conf, int64_
 sonar_voice_quality_result voice_quality_from(const int64_t* ln, const double* amp, const double* f0, int64_t np,
                                               const double* ac, const double* head, int64_t n, int sr, double vstr);
 
+// PitchDetector's postProcessResult + updateTemporalTracking (pitch_detection.go:767-963) for any
+// method and any post-processing parameters: YinTracker above is this at the constructor's defaults,
+// reduced to the three values its callers read.  One step per raw frame, in order; a fresh tracker is a
+// fresh detector (or one after Reset).
+struct PitchTrackParams {
+  bool octave_correction = true, temporal_smoothing = true;
+  int median_filter = 3;           // getRecentPitches(n): n > 20 reads the whole history, n < 1 nothing
+  double min_confidence = 0.5;
+};
+struct PitchRow {
+  double pitch = 0, confidence = 0, voicing = 0, periodicity = 0, clarity = 0, strength = 0, salience = 0,
+         stability = 0, f0_multiple = 0;
+};
+struct PitchTracker {
+  double hist[20] = {0};           // pitchHistory: gated, octave-corrected, unsmoothed; oldest first
+  int count = 0;
+  double prev = 0.0;               // previousPitch: the last smoothed pitch
+  // raw_pitch / raw_conf: what detectPitch* returned (Periodicity = Voicing = Confidence there);
+  // n_candidates = len(Candidates), second_conf = Candidates[1].Confidence when there are two
+  PitchRow step(const PitchTrackParams& p, double raw_pitch, double raw_conf, int n_candidates, double second_conf);
+};
+// AnalyzePitchStability + estimateVibratoRate (:1059-1160): out7 = mean_pitch, pitch_std_dev,
+// coefficient_of_variation, jitter, stability, vibrato_rate, voiced_frames_ratio; false (and zeros) for
+// the empty map of fewer than two entries or fewer than two voiced ones
+bool pitch_stability(const double* pitch, int64_t n, int sample_rate, int hop_size, double out7[7]);
+
 }  // namespace host
 }  // namespace sonar

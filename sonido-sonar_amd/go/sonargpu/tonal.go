@@ -12,6 +12,10 @@ package sonargpu
 // DetectChords and ChordProgressionAnalyzer through sonar_chord_frames, sonar_chord_detect,
 // sonar_chord_sequence and sonar_chord_progression, with the names and strings rebuilt here.
 //
+// PitchDetector seam (algorithms/tonal/pitch_detection.go), after the chord detector: every method of
+// DetectPitch's switch through sonar_pitch_frames_raw, sonar_pitch_track, sonar_pitch_detect and
+// sonar_pitch_stability.
+//
 // Written against include/sonar_gpu.h; not compiled here (no Go toolchain in the image).
 
 /*
@@ -1017,4 +1021,299 @@ func (cpa *ChordProgressionAnalyzer) AnalyzeProgression() (map[string]interface{
 	}
 	return map[string]interface{}{"num_chords": int(num), "transitions": transitions, "average_confidence": float64(avg),
 		"most_common_quality": GetChordQualityName(ChordQuality(most))}, nil
+}
+
+// ---- PitchDetector seam (algorithms/tonal/pitch_detection.go): NewPitchDetector,
+// NewPitchDetectorWithParams, DetectPitch, ProcessAudioStream, Reset, AnalyzePitchStability and
+// GetPitchDetectionMethodName through sonar_pitch_frames_raw, sonar_pitch_track, sonar_pitch_detect and
+// sonar_pitch_stability.  The library returns numbers; this file rebuilds PitchDetectionResult with
+// the method strings of its candidates.  Candidates holds at most 8 entries (SONAR_PITCH's
+// max_candidates limit): the reference returns every peak, the best 8 by confidence are kept here, and
+// equal confidences are ordered by ascending lag where Go's sort.Slice leaves the order open.
+// Harmonics, SNR, HarmonicRatio and ProcessTime are never set by the reference and stay zero.
+
+// PitchDetectionMethod carries the reference's values (:16-35), which are SONAR_PITCH_*.
+type PitchDetectionMethod int
+
+const (
+	AutocorrelationYin PitchDetectionMethod = iota
+	AutocorrelationACF
+	AutocorrelationNSDF
+	FrequencyDomainHPS
+	FrequencyDomainCepstrum
+	FrequencyDomainPeaks
+	TimeDomainZeroCrossing
+	TimeDomainPeakPicking
+	HybridYinFFT
+	HybridMPM
+	HybridPRAATT
+)
+
+const pitchMaxCandidates = 8
+
+// PitchCandidate = tonal.PitchCandidate (:38-44).
+type PitchCandidate struct {
+	Frequency  float64
+	Confidence float64
+	Salience   float64
+	Harmonic   int
+	Method     string
+}
+
+// PitchDetectionResult = tonal.PitchDetectionResult (:47-81).
+type PitchDetectionResult struct {
+	Pitch, Confidence, Salience, Voicing  float64
+	Candidates                            []PitchCandidate
+	Stability, Periodicity                float64
+	Harmonics                             []PitchCandidate
+	F0Multiple                            float64
+	SNR, Clarity, Strength                float64
+	YinThreshold                          float64
+	AutocorrPeaks                         []float64
+	CepstralPeak, HarmonicRatio           float64
+	Method                                PitchDetectionMethod
+	SampleRate, WindowSize                int
+	ProcessTime                           float64
+}
+
+// PitchDetectionParams = tonal.PitchDetectionParams (:84-117).
+type PitchDetectionParams struct {
+	Method                                               PitchDetectionMethod
+	SampleRate, WindowSize, HopSize                      int
+	MinFreq, MaxFreq                                     float64
+	YinThreshold, AutocorrThreshold, CepstralThreshold   float64
+	MinConfidence, MinSalience, VoicingThreshold         float64
+	MaxHarmonics                                         int
+	HarmonicTolerance                                    float64
+	PreEmphasis                                          bool
+	WindowFunction                                       string
+	ZeroPadding                                          int
+	MedianFilter                                         int
+	TemporalSmoothing, OctaveCorrection                  bool
+}
+
+// PitchDetector holds the parameters and, for DetectPitch, the raw rows seen since Reset: the
+// library's tracker starts from an empty history, so a frame-by-frame caller is served by tracking
+// those rows again (exact; O(frames) per call).  ProcessAudioStream on a fresh or Reset detector is one
+// sonar_pitch_detect call.
+type PitchDetector struct {
+	x      *Context
+	params PitchDetectionParams
+	rawP   []float64
+	rawC   []float64
+	rawN   []int32
+	rawS   []float64
+}
+
+// NewPitchDetector = tonal.NewPitchDetector (:159-193), through sonar_pitch_params_default.
+func (x *Context) NewPitchDetector(sampleRate int) *PitchDetector {
+	var p C.sonar_pitch_params
+	C.sonar_pitch_params_default(&p, C.int32_t(sampleRate))
+	return &PitchDetector{x: x, params: PitchDetectionParams{
+		Method: PitchDetectionMethod(p.method), SampleRate: int(p.sample_rate), WindowSize: int(p.window_size),
+		HopSize: int(p.hop_size), MinFreq: float64(p.min_freq), MaxFreq: float64(p.max_freq),
+		YinThreshold: float64(p.yin_threshold), AutocorrThreshold: float64(p.autocorr_threshold),
+		CepstralThreshold: float64(p.cepstral_threshold), MinConfidence: float64(p.min_confidence),
+		MinSalience: float64(p.min_salience), VoicingThreshold: float64(p.voicing_threshold),
+		MaxHarmonics: int(p.max_harmonics), HarmonicTolerance: float64(p.harmonic_tolerance),
+		PreEmphasis: p.pre_emphasis != 0, WindowFunction: "hann", ZeroPadding: int(p.zero_padding),
+		MedianFilter: int(p.median_filter), TemporalSmoothing: p.temporal_smoothing != 0,
+		OctaveCorrection: p.octave_correction != 0}}
+}
+
+// NewPitchDetectorWithParams = tonal.NewPitchDetectorWithParams (:196-207).
+func (x *Context) NewPitchDetectorWithParams(params PitchDetectionParams) *PitchDetector {
+	return &PitchDetector{x: x, params: params}
+}
+
+func (pd *PitchDetector) cParams() C.sonar_pitch_params {
+	p := pd.params
+	win := C.int32_t(C.SONAR_PITCH_WIN_HANN) // createWindowFunction: every unknown string is Hann (:337-342)
+	switch p.WindowFunction {
+	case "hamming":
+		win = C.SONAR_PITCH_WIN_HAMMING
+	case "blackman":
+		win = C.SONAR_PITCH_WIN_BLACKMAN
+	case "rectangular":
+		win = C.SONAR_PITCH_WIN_RECTANGULAR
+	}
+	return C.sonar_pitch_params{method: C.int32_t(p.Method), sample_rate: C.int32_t(p.SampleRate),
+		window_size: C.int32_t(p.WindowSize), hop_size: C.int32_t(p.HopSize), min_freq: C.double(p.MinFreq),
+		max_freq: C.double(p.MaxFreq), yin_threshold: C.double(p.YinThreshold),
+		autocorr_threshold: C.double(p.AutocorrThreshold), cepstral_threshold: C.double(p.CepstralThreshold),
+		min_confidence: C.double(p.MinConfidence), min_salience: C.double(p.MinSalience),
+		voicing_threshold: C.double(p.VoicingThreshold), max_harmonics: C.int32_t(p.MaxHarmonics),
+		harmonic_tolerance: C.double(p.HarmonicTolerance), pre_emphasis: b2i(p.PreEmphasis), window_function: win,
+		zero_padding: C.int32_t(p.ZeroPadding), median_filter: C.int32_t(p.MedianFilter),
+		temporal_smoothing: b2i(p.TemporalSmoothing), octave_correction: b2i(p.OctaveCorrection)}
+}
+
+// candidateMethod is the Method string the reference's detectPitch* writes into its candidates.
+func candidateMethod(m PitchDetectionMethod) string {
+	switch m {
+	case AutocorrelationYin, HybridYinFFT:
+		return "YIN"
+	case AutocorrelationACF:
+		return "ACF"
+	case AutocorrelationNSDF, HybridMPM:
+		return "NSDF"
+	case FrequencyDomainHPS, FrequencyDomainPeaks:
+		return "HPS"
+	case FrequencyDomainCepstrum:
+		return "Cepstrum"
+	case TimeDomainZeroCrossing:
+		return "ZeroCrossing"
+	}
+	return ""
+}
+
+// candidateFrequency turns a candidate's index back into the frequency the reference stores.
+func (pd *PitchDetector) candidateFrequency(index int32, pitch float64, first bool) float64 {
+	switch pd.params.Method {
+	case AutocorrelationACF, AutocorrelationNSDF, HybridMPM:
+		return float64(pd.params.SampleRate) / float64(index)
+	}
+	if first { // one candidate: the frame's own (interpolated, for YIN) pitch
+		return pitch
+	}
+	return 0
+}
+
+// DetectPitch = PitchDetector.DetectPitch (:225-279) on one frame of WindowSize samples.
+func (pd *PitchDetector) DetectPitch(audioFrame []float64) (*PitchDetectionResult, error) {
+	if len(audioFrame) != pd.params.WindowSize {
+		return nil, fmt.Errorf("audio frame size (%d) doesn't match window size (%d)", len(audioFrame), pd.params.WindowSize)
+	}
+	p := pd.cParams()
+	width := int(C.sonar_pitch_curve_width(&p))
+	var pitch, conf, second C.double
+	var index, ncand C.int32_t
+	candI := make([]int32, pitchMaxCandidates)
+	candC := make([]float64, pitchMaxCandidates)
+	var curve []float64
+	var curveP *C.double
+	if width > 0 && pd.params.Method == AutocorrelationACF {
+		curve = make([]float64, width)
+		curveP = f64p(curve)
+	}
+	if rc := C.sonar_pitch_frames_raw(pd.x.c, f64p(audioFrame), C.int64_t(len(audioFrame)), &p, pitchMaxCandidates,
+		&pitch, &conf, &index, &ncand, &second, i32p(candI), f64p(candC), curveP, 0); rc != C.SONAR_OK {
+		return nil, pd.x.err(rc)
+	}
+	pd.rawP = append(pd.rawP, float64(pitch))
+	pd.rawC = append(pd.rawC, float64(conf))
+	pd.rawN = append(pd.rawN, int32(ncand))
+	pd.rawS = append(pd.rawS, float64(second))
+	F := len(pd.rawP)
+	cols := make([][]float64, 9)
+	for k := range cols {
+		cols[k] = make([]float64, F)
+	}
+	if rc := C.sonar_pitch_track(&p, C.int64_t(F), f64p(pd.rawP), f64p(pd.rawC), i32p(pd.rawN), f64p(pd.rawS),
+		f64p(cols[0]), f64p(cols[1]), f64p(cols[2]), f64p(cols[3]), f64p(cols[4]), f64p(cols[5]), f64p(cols[6]),
+		f64p(cols[7]), f64p(cols[8])); rc != C.SONAR_OK {
+		return nil, fmt.Errorf("sonar_pitch_track: %d", int(rc))
+	}
+	r := pd.result(cols, F-1)
+	n := int(ncand)
+	if n > pitchMaxCandidates {
+		n = pitchMaxCandidates
+	}
+	name := candidateMethod(pd.params.Method)
+	for k := 0; k < n; k++ {
+		r.Candidates = append(r.Candidates, PitchCandidate{Frequency: pd.candidateFrequency(candI[k], float64(pitch), k == 0),
+			Confidence: candC[k], Salience: candC[k], Harmonic: 1, Method: name})
+	}
+	switch pd.params.Method {
+	case AutocorrelationYin, HybridYinFFT:
+		r.YinThreshold = pd.params.YinThreshold
+	case AutocorrelationACF:
+		r.AutocorrPeaks = curve
+	case FrequencyDomainCepstrum:
+		r.CepstralPeak = float64(index)
+	}
+	return r, nil
+}
+
+func (pd *PitchDetector) result(cols [][]float64, t int) *PitchDetectionResult {
+	return &PitchDetectionResult{Pitch: cols[0][t], Confidence: cols[1][t], Voicing: cols[2][t], Periodicity: cols[3][t],
+		Clarity: cols[4][t], Strength: cols[5][t], Salience: cols[6][t], Stability: cols[7][t], F0Multiple: cols[8][t],
+		Method: pd.params.Method, SampleRate: pd.params.SampleRate, WindowSize: pd.params.WindowSize}
+}
+
+// ProcessAudioStream = PitchDetector.ProcessAudioStream (:1016-1028).  The frames continue the
+// detector's history, as in the reference.
+func (pd *PitchDetector) ProcessAudioStream(audioFrames [][]float64) ([]*PitchDetectionResult, error) {
+	results := make([]*PitchDetectionResult, len(audioFrames))
+	for i, frame := range audioFrames {
+		r, err := pd.DetectPitch(frame)
+		if err != nil {
+			return nil, fmt.Errorf("error processing frame %d: %v", i, err)
+		}
+		results[i] = r
+	}
+	return results, nil
+}
+
+// ProcessSignal is ProcessAudioStream over the whole frames of one signal (WindowSize samples every
+// HopSize) on a fresh history, in one sonar_pitch_detect call; the results carry no candidates.
+func (pd *PitchDetector) ProcessSignal(pcm []float64) ([]*PitchDetectionResult, error) {
+	p := pd.cParams()
+	F := int(C.sonar_pitch_detect_frames(C.int64_t(len(pcm)), p.window_size, p.hop_size))
+	if F == 0 {
+		return []*PitchDetectionResult{}, nil
+	}
+	cols := make([][]float64, 9)
+	for k := range cols {
+		cols[k] = make([]float64, F)
+	}
+	var frames C.int64_t
+	if rc := C.sonar_pitch_detect(pd.x.c, f64p(pcm), C.int64_t(len(pcm)), &p, f64p(cols[0]), f64p(cols[1]), f64p(cols[2]),
+		f64p(cols[3]), f64p(cols[4]), f64p(cols[5]), f64p(cols[6]), f64p(cols[7]), f64p(cols[8]), &frames, 0); rc != C.SONAR_OK {
+		return nil, pd.x.err(rc)
+	}
+	out := make([]*PitchDetectionResult, F)
+	for t := range out {
+		out[t] = pd.result(cols, t)
+	}
+	return out, nil
+}
+
+// Reset = PitchDetector.Reset (:1031-1035).
+func (pd *PitchDetector) Reset() {
+	pd.rawP, pd.rawC, pd.rawN, pd.rawS = nil, nil, nil, nil
+}
+
+func (pd *PitchDetector) GetParameters() PitchDetectionParams { return pd.params }
+func (pd *PitchDetector) SetParameters(params PitchDetectionParams) { pd.params = params }
+
+// AnalyzePitchStability = PitchDetector.AnalyzePitchStability (:1059-1113); the empty map for fewer
+// than two voiced frames.
+func (pd *PitchDetector) AnalyzePitchStability(pitchSequence []float64) map[string]float64 {
+	analysis := make(map[string]float64)
+	if len(pitchSequence) < 2 {
+		return analysis
+	}
+	var out [7]C.double
+	var empty C.int32_t
+	if rc := C.sonar_pitch_stability(f64p(pitchSequence), C.int64_t(len(pitchSequence)), C.int32_t(pd.params.SampleRate),
+		C.int32_t(pd.params.HopSize), &out[0], &empty); rc != C.SONAR_OK || empty != 0 {
+		return analysis
+	}
+	for k, name := range []string{"mean_pitch", "pitch_std_dev", "coefficient_of_variation", "jitter", "stability",
+		"vibrato_rate", "voiced_frames_ratio"} {
+		analysis[name] = float64(out[k])
+	}
+	return analysis
+}
+
+// GetPitchDetectionMethodName = tonal.GetPitchDetectionMethodName (:1163-1190).
+func GetPitchDetectionMethodName(method PitchDetectionMethod) string {
+	names := []string{"YIN (Autocorrelation)", "Autocorrelation Function", "Normalized Square Difference Function",
+		"Harmonic Product Spectrum", "Cepstral Analysis", "Spectral Peaks", "Zero Crossing Rate", "Peak Picking",
+		"YIN-FFT Hybrid", "McLeod Pitch Method", "PRAAT Algorithm"}
+	if method >= 0 && int(method) < len(names) {
+		return names[method]
+	}
+	return "Unknown"
 }

@@ -371,6 +371,16 @@ def lib():
     L.sonar_xcorr_params.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, _vp, C.c_int32]
     L.sonar_autocorr.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32]
+    L.sonar_pitch_params_default.argtypes = [C.POINTER(PitchParams), C.c_int32]
+    L.sonar_pitch_params_default.restype = None
+    L.sonar_pitch_detect_frames.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.sonar_pitch_detect_frames.restype = C.c_int64
+    L.sonar_pitch_curve_width.argtypes = [C.POINTER(PitchParams)]
+    L.sonar_pitch_curve_width.restype = C.c_int64
+    L.sonar_pitch_frames_raw.argtypes = [_vp, _vp, C.c_int64, C.POINTER(PitchParams), C.c_int32] + [_vp] * 8 + [C.c_int32]
+    L.sonar_pitch_track.argtypes = [C.POINTER(PitchParams), C.c_int64] + [_vp] * 13
+    L.sonar_pitch_detect.argtypes = [_vp, _vp, C.c_int64, C.POINTER(PitchParams)] + [_vp] * 9 + [_i64p, C.c_int32]
+    L.sonar_pitch_stability.argtypes = [_vp, C.c_int64, C.c_int32, C.c_int32, _vp, _i32p]
     L.sonar_music_alignment_features.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_dtw.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, _d, _vp, _vp, _vp, _i64p,
@@ -758,6 +768,97 @@ def hps_plan(n, window_size, hop_size):
 _HPS_OPTIONAL = ("confidence", "strengths", "hps")
 
 
+# PitchDetectionMethod (SONAR_PITCH_*, pitch_detection.go:16-35), createWindowFunction's strings
+# (SONAR_PITCH_WIN_*) and GetPitchDetectionMethodName's names by code
+PITCH_METHODS = {"yin": 0, "acf": 1, "nsdf": 2, "hps": 3, "cepstrum": 4, "peaks": 5, "zero_crossing": 6,
+                 "peak_picking": 7, "yin_fft": 8, "mpm": 9, "praat": 10}
+PITCH_WINDOWS = {"hann": 0, "hamming": 1, "blackman": 2, "rectangular": 3}
+PITCH_METHOD_NAMES = ["YIN (Autocorrelation)", "Autocorrelation Function", "Normalized Square Difference Function",
+                      "Harmonic Product Spectrum", "Cepstral Analysis", "Spectral Peaks", "Zero Crossing Rate",
+                      "Peak Picking", "YIN-FFT Hybrid", "McLeod Pitch Method", "PRAAT Algorithm"]
+PITCH_TRACK_FIELDS = ("pitch", "confidence", "voicing", "periodicity", "clarity", "strength", "salience", "stability",
+                      "f0_multiple")
+PITCH_STABILITY_KEYS = ("mean_pitch", "pitch_std_dev", "coefficient_of_variation", "jitter", "stability",
+                        "vibrato_rate", "voiced_frames_ratio")
+PITCH_MAX_CANDIDATES = 8
+
+
+class PitchParams(C.Structure):
+    """sonar_pitch_params (PitchDetectionParams, pitch_detection.go:84-117, field for field)."""
+    _fields_ = [(n, C.c_int32) for n in ("method", "sample_rate", "window_size", "hop_size")] + \
+               [(n, C.c_double) for n in ("min_freq", "max_freq", "yin_threshold", "autocorr_threshold",
+                                          "cepstral_threshold", "min_confidence", "min_salience",
+                                          "voicing_threshold")] + \
+               [("max_harmonics", C.c_int32), ("harmonic_tolerance", C.c_double)] + \
+               [(n, C.c_int32) for n in ("pre_emphasis", "window_function", "zero_padding", "median_filter",
+                                         "temporal_smoothing", "octave_correction")]
+
+
+def pitch_params_default(sample_rate, **kw):
+    """sonar_pitch_params_default: NewPitchDetector(sample_rate)'s parameters, then the overrides.  method
+    and window_function take their names; a window name Go does not know is Hann, as in
+    createWindowFunction."""
+    p = PitchParams()
+    lib().sonar_pitch_params_default(C.byref(p), int(sample_rate))
+    for k, v in kw.items():
+        if k == "method" and isinstance(v, str):
+            v = PITCH_METHODS[v]
+        if k == "window_function" and isinstance(v, str):
+            v = PITCH_WINDOWS.get(v, 0)
+        if not hasattr(p, k):
+            raise TypeError(f"unknown pitch parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def pitch_method_name(method):
+    """GetPitchDetectionMethodName (:1163-1190)."""
+    return PITCH_METHOD_NAMES[method] if 0 <= method < len(PITCH_METHOD_NAMES) else "Unknown"
+
+
+def pitch_detect_frames(n, window_size, hop_size):
+    """sonar_pitch_detect_frames (host only): the whole frames of n samples."""
+    return int(lib().sonar_pitch_detect_frames(int(n), int(window_size), int(hop_size)))
+
+
+def pitch_curve_width(params):
+    """sonar_pitch_curve_width (host only): the parameter checks and the width of a frame's curve;
+    raises SonarError with the code of a parameter set the entries refuse."""
+    w = int(lib().sonar_pitch_curve_width(C.byref(params)))
+    if w < 0:
+        raise SonarError(w, "unsupported pitch detection method: %d" % params.method
+                         if w == ERR_INVALID and params.method not in (0, 1, 2, 3, 4, 5, 6, 8, 9)
+                         else "pitch detection: parameters refused (include/sonar_gpu.h)")
+    return w
+
+
+def pitch_track(params, raw_pitch, raw_confidence, n_candidates=None, second_confidence=None):
+    """sonar_pitch_track (host only): postProcessResult + updateTemporalTracking over raw rows in order,
+    from an empty history -> dict of PITCH_TRACK_FIELDS."""
+    rp, rc_ = _f64(raw_pitch), _f64(raw_confidence)
+    F = len(rp)
+    nc = None if n_candidates is None else np.ascontiguousarray(n_candidates, dtype=np.int32)
+    sc = None if second_confidence is None else _f64(second_confidence)
+    out = {k: np.zeros(F) for k in PITCH_TRACK_FIELDS}
+    rc = lib().sonar_pitch_track(C.byref(params), F, _ptr(rp), _ptr(rc_), _ptr(nc), _ptr(sc),
+                                 *[_ptr(out[k]) for k in PITCH_TRACK_FIELDS])
+    if rc != OK:
+        raise SonarError(rc, "sonar_pitch_track")
+    return out
+
+
+def pitch_stability(pitch, sample_rate, hop_size=512):
+    """sonar_pitch_stability (host only): AnalyzePitchStability -> dict of PITCH_STABILITY_KEYS, or {} for
+    the empty map Go returns with fewer than two voiced frames."""
+    p = _f64(pitch)
+    out, empty = np.zeros(7), C.c_int32()
+    rc = lib().sonar_pitch_stability(_ptr(p) if len(p) else None, len(p), int(sample_rate), int(hop_size), _ptr(out),
+                                     C.byref(empty))
+    if rc != OK:
+        raise SonarError(rc, "sonar_pitch_stability")
+    return {} if empty.value else dict(zip(PITCH_STABILITY_KEYS, out.tolist()))
+
+
 _ONSET_ERRORS = {ERR_UNSUPPORTED: "onsets: parameters the library does not reproduce (include/sonar_gpu.h)",
                  ERR_INVALID: "onsets: invalid argument"}
 
@@ -1078,6 +1179,52 @@ class Context:
         p, c, t = np.zeros(F), np.zeros(F), np.zeros(F, np.int32)
         self._check(self._L.sonar_pitch_yin(self._h, _ptr(pcm), len(pcm), sample_rate, _ptr(p), _ptr(c), _ptr(t), 0))
         return p, c, t
+
+    def pitch_frames_raw(self, pcm, params, max_candidates=PITCH_MAX_CANDIDATES, want_curve=True):
+        """DetectPitch up to postProcessResult per whole frame of pcm (sonar_pitch_frames_raw) -> dict of
+        pitch, confidence, index, n_candidates, second_confidence, cand_index, cand_conf (F x
+        max_candidates) and curve (F x pitch_curve_width(params), when wanted)."""
+        pcm = _f64(pcm)
+        F = pitch_detect_frames(len(pcm), params.window_size, params.hop_size)
+        K = int(max_candidates)
+        width = max(int(self._L.sonar_pitch_curve_width(C.byref(params))), 0)
+        out = {"pitch": np.zeros(F), "confidence": np.zeros(F), "index": np.zeros(F, np.int32),
+               "n_candidates": np.zeros(F, np.int32), "second_confidence": np.zeros(F),
+               "cand_index": np.zeros((F, max(K, 0)), np.int32), "cand_conf": np.zeros((F, max(K, 0))),
+               "curve": np.zeros((F, width)) if want_curve else None}
+        self._check(self._L.sonar_pitch_frames_raw(self._h, _ptr(pcm) if len(pcm) else None, len(pcm), C.byref(params), K,
+                                                   *[_ptr(out[k]) for k in ("pitch", "confidence", "index",
+                                                                            "n_candidates", "second_confidence",
+                                                                            "cand_index", "cand_conf", "curve")], 0))
+        return out
+
+    def pitch_frames_raw_device(self, pcm_ptr, n, params, pitch_ptr, confidence_ptr, max_candidates=0, index_ptr=None,
+                                n_candidates_ptr=None, second_confidence_ptr=None, cand_index_ptr=None,
+                                cand_conf_ptr=None, curve_ptr=None):
+        """pitch_frames_raw on device memory (device_ptrs = 1): every array is a device address."""
+        self._check(self._L.sonar_pitch_frames_raw(self._h, pcm_ptr, int(n), C.byref(params), int(max_candidates),
+                                                   pitch_ptr, confidence_ptr, index_ptr, n_candidates_ptr,
+                                                   second_confidence_ptr, cand_index_ptr, cand_conf_ptr, curve_ptr, 1))
+
+    def pitch_detect(self, pcm, params):
+        """ProcessAudioStream over the whole frames of pcm (sonar_pitch_detect): the raw pass, then the
+        tracker -> dict of PITCH_TRACK_FIELDS."""
+        pcm = _f64(pcm)
+        F = pitch_detect_frames(len(pcm), params.window_size, params.hop_size)
+        out = {k: np.zeros(F) for k in PITCH_TRACK_FIELDS}
+        frames = C.c_int64()
+        self._check(self._L.sonar_pitch_detect(self._h, _ptr(pcm) if len(pcm) else None, len(pcm), C.byref(params),
+                                               *[_ptr(out[k]) for k in PITCH_TRACK_FIELDS], C.byref(frames), 0))
+        assert frames.value == F
+        return out
+
+    def pitch_detect_device(self, pcm_ptr, n, params, out_ptrs):
+        """pitch_detect on device memory (device_ptrs = 1): out_ptrs maps names of PITCH_TRACK_FIELDS to
+        device addresses of F doubles (missing: not wanted) -> the frame count."""
+        frames = C.c_int64()
+        self._check(self._L.sonar_pitch_detect(self._h, pcm_ptr, int(n), C.byref(params),
+                                               *[out_ptrs.get(k) for k in PITCH_TRACK_FIELDS], C.byref(frames), 1))
+        return frames.value
 
     def chroma_stft(self, pcm, n_frames, hop, sample_rate, preprocess=True):
         pcm = _f64(pcm)
