@@ -13,6 +13,7 @@
 
 #include "ctx.h"
 #include "kernels.h"
+#include "magnitude_walk.h"
 #include "staging.h"
 
 using sonar::detail::fail;
@@ -110,10 +111,9 @@ int run(sonar_ctx* c, Staging& o, sonar::ChordArgs& a, const sonar_chord_params&
     kidx = o.tmp<int32_t>("kidx", (size_t)F + 1);
     if (history) kconf = o.tmp<double>("kconf", (size_t)F);
   }
-  a.flags = o.tmp<int32_t>("flag", 1);
+  a.flags = o.flag();
   int rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
-  HIP_TRY(c, hipMemsetAsync(a.flags, 0, 4, s));
   hipEvent_t tend = timed_begin(c, s);
   if (chain) {
     sonar::ChordArgs r = a;
@@ -133,10 +133,9 @@ int run(sonar_ctx* c, Staging& o, sonar::ChordArgs& a, const sonar_chord_params&
   if (kconf && sonar::launch_chord_stability(kidx, kconf, F, p.temporal_window, a.stability, s) != 0)
     return fail(c, SONAR_ERR_DEVICE, "chord stability launch failed");
   timed_end(c, s, tend);
-  int32_t flags = 0;
-  HIP_TRY(c, hipMemcpyAsync(&flags, a.flags, 4, hipMemcpyDeviceToHost, s));
   rc = o.finish();
   if (rc != SONAR_OK) return rc;
+  const int32_t flags = o.flags();
   if (flags & sonar::CHORD_FLAG_BASS_NOTE) return fail(c, SONAR_ERR_INVALID, "chord detection: a bass note outside 0..11");
   if (flags & sonar::CHORD_FLAG_NONFINITE)
     return fail(c, SONAR_ERR_UNSUPPORTED,
@@ -226,32 +225,20 @@ int sonar_chord_detect(sonar_ctx* c, const double* pcm, int64_t n, int32_t sampl
     return fail(c, SONAR_ERR_UNSUPPORTED,
                 "chord detection: at frame length 1024 with use_bass_detection the bass arrays must be given "
                 "(the pitch detector's state is not reproduced)");
-  sonar_fp_cfg cfg;
-  sonar_fp_cfg_default(&cfg);
-  cfg.window_size = W;
-  cfg.hop_size = hop;
-  cfg.window_type = SONAR_WIN_RECTANGULAR;
-  cfg.sample_rate = sample_rate;
-  cfg.flags = SONAR_FP_MAGNITUDE;
-  cfg.precision = SONAR_F64;
-  cfg.pcm_dtype = SONAR_F64;
-  cfg.out_dtype = SONAR_F64;
-  cfg.device_ptrs = 1;
   const int64_t used = (F - 1) * (int64_t)hop + W;          // every frame's first W samples lie inside it
-  int64_t F2 = 0;
-  rc = sonar::detail::fp_check(&cfg, used, pcm != nullptr, &F2, &msg);
+  sonar::detail::MagnitudeWalk walk;
+  rc = walk.plan(sample_rate, W, hop, SONAR_WIN_RECTANGULAR, used, pcm != nullptr, &msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
-  if (F2 != F) return fail(c, SONAR_ERR_UNSUPPORTED, "chord detection: the STFT path frames this signal differently");
+  if (walk.F != F) return fail(c, SONAR_ERR_UNSUPPORTED, "chord detection: the STFT path frames this signal differently");
+  walk.chunk_frames = std::max<int64_t>(kDetectChunkBytes / ((int64_t)W * 8), 1);
   if (frames) *frames = F;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   Staging o{c, "chord.", device_ptrs != 0};
   const double* dx = o.in("pcm", pcm, (size_t)n);
   double* dh = hpcp ? o.out("hpcp", hpcp, (size_t)F * 12) : o.tmp<double>("hpcp", (size_t)F * 12);
-  const int32_t K = W / 2 + 1;
-  const int64_t cf = std::min<int64_t>(std::max<int64_t>(kDetectChunkBytes / ((int64_t)W * 8), 1), F);
-  double* half = o.tmp<double>("half", (size_t)cf * (size_t)K);
-  double* full = o.tmp<double>("full", (size_t)cf * (size_t)W);
+  walk.alloc(o, 0, "half");
+  double* full = o.tmp<double>("full", (size_t)std::min(walk.chunk_frames, F) * (size_t)W);
   sonar::ChordArgs a{};
   base_args(p, 12, a);
   a.F = F;
@@ -265,17 +252,11 @@ int sonar_chord_detect(sonar_ctx* c, const double* pcm, int64_t n, int32_t sampl
   if (rc != SONAR_OK) return rc;
   sonar_hpcp_params hp;
   sonar_hpcp_params_default(&hp);                           // NewHPCP(sampleRate) (:255)
-  for (int64_t f0 = 0; f0 < F; f0 += cf) {
-    const int64_t nf = std::min(cf, F - f0);
-    sonar_fp_out fo;
-    std::memset(&fo, 0, sizeof fo);
-    fo.magnitude = half;
-    rc = sonar::detail::fingerprint_impl(c, dx + f0 * hop, (nf - 1) * (int64_t)hop + W, &cfg, &fo, true);
-    if (rc != SONAR_OK) return rc;
+  rc = walk.each(c, dx, used, false, [&](const double* half, int64_t f0, int64_t nf) {
     if (sonar::launch_chord_mirror(half, nf, W, full, s) != 0) return fail(c, SONAR_ERR_DEVICE, "chord mirror launch failed");
-    rc = sonar_hpcp_from_spectrum(c, full, nf, W, W, sample_rate, &hp, dh + f0 * 12, nullptr, nullptr, 1);
-    if (rc != SONAR_OK) return rc;
-  }
+    return sonar_hpcp_from_spectrum(c, full, nf, W, W, sample_rate, &hp, dh + f0 * 12, nullptr, nullptr, 1);
+  });
+  if (rc != SONAR_OK) return rc;
   return run(c, o, a, p, true);
 }
 
@@ -294,33 +275,29 @@ int sonar_chord_progression(sonar_ctx* c, const int32_t* root, const int32_t* qu
   if (!c) return SONAR_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
+  Staging o{c, "chordprog.", device_ptrs != 0};
   if (device_ptrs) {
-    if (num_chords) HIP_TRY(c, hipMemcpyAsync(num_chords, &F, 8, hipMemcpyHostToDevice, s));
-    if (insufficient_data) HIP_TRY(c, hipMemcpyAsync(insufficient_data, &insufficient, 4, hipMemcpyHostToDevice, s));
-    if (insufficient) {
-      HIP_TRY(c, hipStreamSynchronize(s));
-      return SONAR_OK;
-    }
+    int rc = o.put(num_chords, &F, 8);
+    if (rc == SONAR_OK) rc = o.put(insufficient_data, &insufficient, 4);
+    if (rc != SONAR_OK) return rc;
+    if (insufficient) return o.finish();                    // nothing to copy back: the wait for the two uploads
   }
   if (F > INT32_MAX) return fail(c, SONAR_ERR_UNSUPPORTED, "chord progression: more than 2^31 - 1 chords are not supported");
   if (!quality || !confidence) return fail(c, SONAR_ERR_INVALID, "chord progression: null quality or confidence pointer");
-  Staging o{c, "chordprog.", device_ptrs != 0};
   const int32_t* dq = o.in("quality", quality, (size_t)F);
   const double* dc = o.in("conf", confidence, (size_t)F);
   double* davg = o.out("avg", average_confidence, 1);
   int32_t* dmost = o.out("most", most_common_quality, 1);
-  int32_t* dflags = o.tmp<int32_t>("flag", 1);
+  int32_t* dflags = o.flag();
   int rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
-  HIP_TRY(c, hipMemsetAsync(dflags, 0, 4, s));
   hipEvent_t tend = timed_begin(c, s);
   if (sonar::launch_chord_progression(dq, dc, F, davg, dmost, dflags, s) != 0)
     return fail(c, SONAR_ERR_DEVICE, "chord progression launch failed");
   timed_end(c, s, tend);
-  int32_t flags = 0;
-  HIP_TRY(c, hipMemcpyAsync(&flags, dflags, 4, hipMemcpyDeviceToHost, s));
   rc = o.finish();
   if (rc != SONAR_OK) return rc;
+  const int32_t flags = o.flags();
   if (flags & sonar::CHORD_FLAG_QUALITY) return fail(c, SONAR_ERR_UNSUPPORTED, "chord progression: a quality code outside 0..31");
   if (flags & sonar::CHORD_FLAG_NONFINITE) return fail(c, SONAR_ERR_UNSUPPORTED, "chord progression: a non-finite confidence");
   return SONAR_OK;

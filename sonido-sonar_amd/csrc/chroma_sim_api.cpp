@@ -204,11 +204,10 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   unsigned long long* red = (unsigned long long*)dbuf(c, "csim.red", 32);   // sum | count | max bits | spare
   if (!rp || !red) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (chroma similarity)");
   Stages st{c, s};
-  std::vector<uint8_t> skip;                         // lives until the final synchronisation
   const double* qp = nullptr;
 
   // the 12 ordered sums of findBestTransposition (banded = 0) or OTI (banded = 1) -> host
-  double tot[12];
+  const double* tot = nullptr;
   auto ordered = [&](int banded) -> int {
     double* q12 = (double*)dbuf(c, "csim.q12", (size_t)12 * nq * rl * 8);
     double* dt = (double*)dbuf(c, "csim.tot", 12 * 8);
@@ -217,15 +216,14 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
     if (sonar::launch_chroma_prepare(dq, nq, dim, metric, 0, 12, q12, s) ||
         sonar::launch_chroma_prepare(dr, nr, dim, metric, 0, 1, rp, s))
       return fail(c, SONAR_ERR_DEVICE, "chroma prepare launch failed");
-    sonar::ChromaOrdArgs o{};
-    o.qp = q12; o.rp = rp; o.nq = nq; o.nr = nr; o.dim = dim; o.metric = metric;
-    o.step = banded ? 1 : sample_step(nq); o.banded = banded; o.radius = oti_radius; o.totals = dt;
-    if (sonar::launch_chroma_ordered(o, s) != 0) return fail(c, SONAR_ERR_DEVICE, "chroma ordered-sum launch failed");
+    sonar::ChromaOrdArgs a{};
+    a.qp = q12; a.rp = rp; a.nq = nq; a.nr = nr; a.dim = dim; a.metric = metric;
+    a.step = banded ? 1 : sample_step(nq); a.banded = banded; a.radius = oti_radius; a.totals = dt;
+    if (sonar::launch_chroma_ordered(a, s) != 0) return fail(c, SONAR_ERR_DEVICE, "chroma ordered-sum launch failed");
     st.end(1);
-    HIP_TRY(c, hipMemcpyAsync(tot, dt, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    tot = o.back(dt, 12);
     qp = q12;
-    return SONAR_OK;
+    return o.fetch();
   };
   // the first shift whose mean is strictly greater than the running best, from 0.0 (:471-475, :429-434)
   auto pick = [&](double count, double* mx) {
@@ -310,8 +308,7 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
       return fail(c, SONAR_ERR_DEVICE, "chroma reduction launch failed");
     timed_end(c, s, tend);
     st.end(0);
-    unsigned long long h[3];
-    HIP_TRY(c, hipMemcpyAsync(h, red, sizeof h, hipMemcpyDeviceToHost, s));
+    const unsigned long long* h = o.back(red, 3);
     if (const int rc = o.finish()) return rc;
     st.finish();
     double sum, mx;
@@ -352,14 +349,12 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   int64_t* dscal = (int64_t*)red;                    // [0] best score, [1] its index, [2] path length, [3] acc end
   if (dtw) {
     if (dtw_band_radius > 0 && nq >= 2) {
-      skip.assign((size_t)nr, 0);
+      std::vector<uint8_t> skip((size_t)nr, 0);
       bool any = false;
       for (int64_t j = 1; j < nr; ++j) any |= (skip[(size_t)j] = dtw_skips(j, nq, nr, dtw_band_radius));
-      if (any) {
-        uint8_t* ds = (uint8_t*)dbuf(c, "csim.skip", (size_t)nr);
-        if (!ds) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (band mask)");
-        HIP_TRY(c, hipMemcpyAsync(ds, skip.data(), (size_t)nr, hipMemcpyHostToDevice, s));
-        d.skip = ds;
+      if (any) {                                     // the mask goes up from a copy of it that o keeps
+        d.skip = o.in_host("skip", skip.data(), (size_t)nr);
+        if (const int rc = o.ready("device allocation failed (band mask)")) return rc;
       }
     }
   } else {
@@ -379,11 +374,11 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   if (sonar::launch_chroma_traceback(M, d.tb, nq, nr, dtw, dscal + 1, pq, pr, ps, cap, dscal + 2, s) != 0)
     return fail(c, SONAR_ERR_DEVICE, "chroma traceback launch failed");
   st.end(3);
-  double best_score = 0.0, acc_end = 0.0;
-  if (dtw) HIP_TRY(c, hipMemcpyAsync(&acc_end, M + cells - 1, 8, hipMemcpyDeviceToHost, s));
-  else HIP_TRY(c, hipMemcpyAsync(&best_score, dscal, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(&P, dscal + 2, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  // SW: the best score; DTW: acc[nq-1][nr-1]
+  const double* end = o.back(dtw ? M + cells - 1 : (const double*)dscal, 1);
+  const int64_t* plen = o.back(dscal + 2, 1);
+  if (const int rc = o.fetch()) return rc;
+  P = *plen;
   if (P > 0) {                                       // written back to front: the path is the tail
     if (const int rc = o.give(path_q, pq + cap - P, (size_t)P * 4)) return rc;
     if (const int rc = o.give(path_r, pr + cap - P, (size_t)P * 4)) return rc;
@@ -392,7 +387,7 @@ int sonar_chroma_similarity(sonar_ctx* c, const double* q, int64_t nq, const dou
   if (const int rc = o.finish()) return rc;
   st.finish();
   // SW: maxScore / len(path) (:261); DTW: exp(-(acc[nq-1][nr-1] / len(path))) (:341-342)
-  ov = dtw ? std::exp(-(acc_end / (double)P)) : best_score / (double)P;
+  ov = dtw ? std::exp(-(*end / (double)P)) : *end / (double)P;
   return done();
 }
 

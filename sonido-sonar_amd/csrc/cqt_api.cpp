@@ -198,16 +198,14 @@ int sonar_chroma_cqt(sonar_ctx* c, const double* pcm, int64_t n, int64_t hop, in
   const size_t cqt_count = (size_t)p.F * (size_t)p.K;
   double* dq = cqt ? o.out("out", cqt, cqt_count) : o.tmp<double>("out", cqt_count);
   double* dc = o.out("chroma", chroma, (size_t)p.F * 12);
-  int32_t* flag = o.tmp<int32_t>("flag", 4);
+  int32_t* flag = o.flag();
   const int src = o.ready("device allocation failed");
   if (src != SONAR_OK) return src;
   // non-finite PCM is refused before any output is written
-  int32_t hflag = 0;
-  HIP_TRY(c, hipMemsetAsync(flag, 0, 4, s));
   if (sonar::launch_nonfinite(dx, n, flag, s) != 0) return fail(c, SONAR_ERR_DEVICE, "chroma CQT launch failed");
-  HIP_TRY(c, hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  if (hflag)
+  const int frc = o.fetch();
+  if (frc != SONAR_OK) return frc;
+  if (o.flags())
     return fail(c, SONAR_ERR_UNSUPPORTED, "chroma CQT: non-finite PCM is not reproduced (the reference spreads it through its FFT)");
   sonar::CqtArgs a{};
   a.x = dx; a.n = n; a.hop = hop; a.F = p.F;

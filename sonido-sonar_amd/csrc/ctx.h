@@ -225,12 +225,6 @@ int fingerprint_impl(sonar_ctx* c, const void* pcm, int64_t n, const sonar_fp_cf
                      bool pcm_dev, int64_t f_lo = 0, int64_t f_hi = -1, bool raw_window = false);
 // sonar_fingerprint's argument checks in its order: SONAR_OK and the frame count, or the code and text
 int fp_check(const sonar_fp_cfg* cfg, int64_t n, bool have_pcm, int64_t* F, std::string* msg);
-// The entries that run rows of |X| through a bounded scratch (sonar_hpcp, sonar_hps; hpcp_api.cpp):
-// the transform's configuration (SONAR_FP_MAGNITUDE only, float64 all through, device pointers) and
-// the rows per chunk, about 64 MiB of them
-void magnitude_fp_cfg(int32_t sample_rate, int32_t window_size, int32_t hop_size, int32_t window_type,
-                      sonar_fp_cfg* cfg);
-int64_t magnitude_chunk_frames(int32_t window_size);
 // VoiceQualityAnalyzer.AnalyzeVoiceQuality on device-resident float64 samples (voice_api.cpp)
 int voice_quality(sonar_ctx* c, const double* dsig, int64_t n, int32_t sr, sonar_voice_quality_result* out);
 }  // namespace detail

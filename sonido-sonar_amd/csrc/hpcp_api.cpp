@@ -4,8 +4,8 @@
 // the contribution table (frequencyToPitchClass :224-236, addPeakContribution :254-281,
 // computeWindowWeight :284-300, addHarmonicContributions :303-321, evaluated per FFT bin with libm)
 // as one cached table per parameter set (ctx.h, cached_table), the staged arrays of each entry
-// (staging.h), and sonar_hpcp's chunk loop over the float64 transform.  The kernel is
-// hpcp_kernels.hip's.
+// (staging.h), and sonar_hpcp's profile over the chunked walk of the float64 transform
+// (magnitude_walk.h).  The kernel is hpcp_kernels.hip's.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -17,10 +17,12 @@
 #include "ctx.h"
 #include "go_math.h"
 #include "kernels.h"
+#include "magnitude_walk.h"
 #include "staging.h"
 
 using sonar::go_log2;
 using sonar::detail::fail;
+using sonar::detail::MagnitudeWalk;
 using sonar::detail::Staging;
 using sonar::detail::timed_begin;
 using sonar::detail::timed_end;
@@ -30,7 +32,6 @@ namespace {
 constexpr int64_t kMaxEntries = int64_t(1) << 24;
 constexpr int32_t kMaxHarmonics = 16;
 constexpr double kMaxWindowSemitones = 12.0;
-constexpr int64_t kChunkBytes = int64_t(64) << 20;   // sonar_hpcp's magnitude scratch
 // ComputeFromSpectrum's detector (:211-216)
 constexpr double kHpcpMinHeight = 0.00001, kHpcpMinDistanceHz = 20.0;
 constexpr int32_t kHpcpMaxPeaks = 60;
@@ -235,31 +236,6 @@ int profile_rows(sonar_ctx* c, const double* dmag, int64_t F, int32_t K, int32_t
 
 }  // namespace
 
-namespace sonar {
-namespace detail {
-void magnitude_fp_cfg(int32_t sample_rate, int32_t window_size, int32_t hop_size, int32_t window_type, sonar_fp_cfg* cfg) {
-  sonar_fp_cfg_default(cfg);
-  cfg->window_size = window_size;
-  cfg->hop_size = hop_size;
-  cfg->window_type = window_type;
-  cfg->sample_rate = sample_rate;
-  cfg->flags = SONAR_FP_MAGNITUDE;
-  cfg->precision = SONAR_F64;
-  cfg->pcm_dtype = SONAR_F64;
-  cfg->out_dtype = SONAR_F64;
-  cfg->device_ptrs = 1;
-}
-
-int64_t magnitude_chunk_frames(int32_t window_size) {
-  const int64_t K = window_size / 2 + 1;
-  return std::max<int64_t>(kChunkBytes / (K * 8), 1);
-}
-}  // namespace detail
-}  // namespace sonar
-
-using sonar::detail::magnitude_chunk_frames;
-using sonar::detail::magnitude_fp_cfg;
-
 extern "C" {
 
 int64_t sonar_spectral_peaks_width(int64_t K, int64_t max_peaks) { return peaks_width(K, max_peaks); }
@@ -371,22 +347,18 @@ int sonar_hpcp_from_spectrum(sonar_ctx* c, const double* mag, int64_t F, int32_t
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   rc = profile_rows(c, dm, F, K, window_size, sample_rate, p, T, dh, de, dn);
-  if (rc != SONAR_OK) return rc;
-  return o.finish();
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 int sonar_hpcp_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* frames, int64_t* chunk_frames,
                     int64_t* n_chunks) {
-  sonar_fp_cfg cfg;
-  magnitude_fp_cfg(44100, window_size, hop_size, SONAR_WIN_HANN, &cfg);
-  int64_t F = 0;
+  MagnitudeWalk walk;
   std::string msg;
-  const int rc = sonar::detail::fp_check(&cfg, n, true, &F, &msg);
+  const int rc = walk.plan(44100, window_size, hop_size, SONAR_WIN_HANN, n, true, &msg);
   if (rc != SONAR_OK) return rc;
-  const int64_t cf = magnitude_chunk_frames(window_size);
-  if (frames) *frames = F;
-  if (chunk_frames) *chunk_frames = cf;
-  if (n_chunks) *n_chunks = (F + cf - 1) / cf;
+  if (frames) *frames = walk.F;
+  if (chunk_frames) *chunk_frames = walk.chunk_frames;
+  if (n_chunks) *n_chunks = (walk.F + walk.chunk_frames - 1) / walk.chunk_frames;
   return SONAR_OK;
 }
 
@@ -395,14 +367,14 @@ int sonar_hpcp(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, 
                int32_t device_ptrs) {
   if (!c) return SONAR_ERR_INVALID;
   if (!params) return fail(c, SONAR_ERR_INVALID, "HPCP: null params");
-  sonar_fp_cfg cfg;
-  magnitude_fp_cfg(sample_rate, window_size, hop_size, window_type, &cfg);
-  int64_t F = 0;
+  MagnitudeWalk walk;
   std::string msg;
-  int rc = sonar::detail::fp_check(&cfg, n, pcm != nullptr, &F, &msg);   // ComputeSTFTWithWindow's checks first
+  // ComputeSTFTWithWindow's checks first
+  int rc = walk.plan(sample_rate, window_size, hop_size, window_type, n, pcm != nullptr, &msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
   const sonar_hpcp_params& p = *params;
-  const int32_t K = window_size / 2 + 1;
+  const int64_t F = walk.F;
+  const int32_t K = walk.K;
   rc = check_params(p, msg);
   if (rc == SONAR_OK) rc = check_rates(sample_rate, window_size, K, msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
@@ -418,26 +390,16 @@ int sonar_hpcp(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, 
   double* dh = o.out("out", hpcp, (size_t)F * (size_t)p.size);
   double* de = o.out("energy", energy, (size_t)F);
   double* dn = o.out("entropy", entropy, (size_t)F);
+  walk.alloc(o);
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
-  // Chunks of chunk_frames rows through one bounded scratch: the transform of the chunk's samples
-  // (frame f of the signal is frame f - f0 of the samples from f0 * hop on: every frame lies inside
-  // the signal), then the profile of its rows; both are queued on the context's stream, so the
-  // scratch is reused in stream order and the host waits once, at the end.
-  const int64_t cf = magnitude_chunk_frames(window_size);
-  double* scratch = o.tmp<double>("chunk", (size_t)std::min(cf, F) * (size_t)K);
-  if (!scratch) return fail(c, SONAR_ERR_NOMEM, "device allocation failed (HPCP magnitude scratch)");
-  for (int64_t f0 = 0; p.size > 0 && f0 < F; f0 += cf) {
-    const int64_t nf = std::min(cf, F - f0);
-    sonar_fp_out out;
-    std::memset(&out, 0, sizeof out);
-    out.magnitude = scratch;
-    rc = sonar::detail::fingerprint_impl(c, dx + f0 * hop_size, (nf - 1) * hop_size + window_size, &cfg, &out, true);
-    if (rc != SONAR_OK) return rc;
-    rc = profile_rows(c, scratch, nf, K, window_size, sample_rate, p, T, dh + f0 * p.size, de ? de + f0 : nullptr,
-                      dn ? dn + f0 : nullptr);
-    if (rc != SONAR_OK) return rc;
-  }
+  // the profile of every chunk's rows; the host waits once, at the end
+  if (p.size > 0)
+    rc = walk.each(c, dx, n, false, [&](const double* rows, int64_t f0, int64_t nf) {
+      return profile_rows(c, rows, nf, K, window_size, sample_rate, p, T, dh + f0 * p.size, de ? de + f0 : nullptr,
+                          dn ? dn + f0 : nullptr);
+    });
+  if (rc != SONAR_OK) return rc;
   if (p.size == 0) {                                        // the staged copies are device memory in both modes
     for (double* z : {de, dn}) {
       const int zrc = sonar::detail::zero_out(c, z, (size_t)F * 8, true);

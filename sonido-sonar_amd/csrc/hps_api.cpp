@@ -1,16 +1,16 @@
 // hps_api.cpp -- sonar_hps_from_spectrum, sonar_hps and their host-only companions: HarmonicProduct
 // (algorithms/harmonic/harmonic_product.go).  The host side: the argument checks, findF0Peak's scan
 // range (:128-139, a function of the parameters alone), GetOptimalNumHarmonics (:301-314), the staged
-// arrays of each entry (staging.h) and sonar_hps's chunk loop over the float64 transform with
-// applyWindow's window (:212-221).  The kernels are hps_kernels.hip's.
+// arrays of each entry (staging.h) and sonar_hps's estimate over the chunked walk of the float64
+// transform (magnitude_walk.h) with applyWindow's window (:212-221).  The kernels are hps_kernels.hip's.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 #include <string>
 
 #include "ctx.h"
 #include "kernels.h"
+#include "magnitude_walk.h"
 #include "staging.h"
 
 using sonar::detail::fail;
@@ -166,8 +166,7 @@ int sonar_hps_from_spectrum(sonar_ctx* c, const double* mag, int64_t F, int32_t 
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   rc = estimate_rows(c, dm, F, K, window_size, sample_rate, num_harmonics, clamp_range(r, K), interpolated, out, total);
-  if (rc != SONAR_OK) return rc;
-  return o.finish();
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 int sonar_hps_plan(int64_t n, int32_t window_size, int32_t hop_size, int64_t* frames, int64_t* chunk_frames,
@@ -181,15 +180,15 @@ int sonar_hps(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, i
               int32_t num_harmonics, double min_f0, double max_f0, int32_t interpolated, int32_t* f0_bin, double* f0,
               double* confidence, double* strengths, double* magnitude, int64_t* frames, int32_t device_ptrs) {
   if (!c) return SONAR_ERR_INVALID;
-  sonar_fp_cfg cfg;
-  sonar::detail::magnitude_fp_cfg(sample_rate, window_size, hop_size, SONAR_WIN_HANN, &cfg);
-  int64_t F = 0;
+  sonar::detail::MagnitudeWalk walk;
   std::string msg;
-  int rc = sonar::detail::fp_check(&cfg, n, pcm != nullptr, &F, &msg);   // the transform's checks first, as sonar_hpcp
+  // the transform's checks first, as sonar_hpcp
+  int rc = walk.plan(sample_rate, window_size, hop_size, SONAR_WIN_HANN, n, pcm != nullptr, &msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
   if (window_size < 2)
     return fail(c, SONAR_ERR_UNSUPPORTED, "harmonic product: a window of fewer than 2 samples is not reproduced");
-  const int32_t K = window_size / 2 + 1;
+  const int64_t F = walk.F;
+  const int32_t K = walk.K;
   Range r{};
   rc = scan_range(sample_rate, window_size, min_f0, max_f0, &r, msg);
   if (rc == SONAR_OK) rc = check_shape(K, num_harmonics, confidence || strengths, msg);
@@ -205,32 +204,20 @@ int sonar_hps(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, i
   out.f0 = o.out("f0", f0, (size_t)F);
   out.confidence = o.out("confidence", confidence, (size_t)F);
   out.strengths = nh ? o.out("strengths", strengths, (size_t)F * nh) : nullptr;
-  // Chunks of chunk_frames rows through one bounded scratch, as sonar_hpcp: the transform of the
-  // chunk's samples under applyWindow's window, the estimate of its rows and, when the caller wants
-  // the rows, their copy out, all queued on the context's stream; the host waits once, at the end.
-  const int64_t cf = sonar::detail::magnitude_chunk_frames(window_size);
-  const size_t chunk = (size_t)std::min(cf, F);
-  double* scratch = o.tmp<double>("chunk", chunk * (size_t)K);
-  double* total = confidence && rows_per_lane((int64_t)chunk) ? o.tmp<double>("total", chunk) : nullptr;
+  walk.alloc(o);
+  const int64_t chunk = std::min(walk.chunk_frames, F);
+  double* total = confidence && rows_per_lane(chunk) ? o.tmp<double>("total", (size_t)chunk) : nullptr;
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   r = clamp_range(r, K);
-  for (int64_t s0 = 0; s0 < F; s0 += cf) {
-    const int64_t nf = std::min(cf, F - s0);
-    sonar_fp_out fo;
-    std::memset(&fo, 0, sizeof fo);
-    fo.magnitude = scratch;
-    rc = sonar::detail::fingerprint_impl(c, dx + s0 * hop_size, (nf - 1) * hop_size + window_size, &cfg, &fo, true, 0,
-                                         -1, true);
-    if (rc != SONAR_OK) return rc;
+  // under applyWindow's window: every chunk's estimate and, if wanted, its rows' copy out; one wait, at the end
+  rc = walk.each(c, dx, n, true, [&](const double* rows, int64_t s0, int64_t nf) {
     RowOut part{out.f0_bin + s0, out.f0 + s0, out.confidence ? out.confidence + s0 : nullptr,
                 out.strengths ? out.strengths + s0 * (int64_t)nh : nullptr, nullptr};
-    rc = estimate_rows(c, scratch, nf, K, window_size, sample_rate, num_harmonics, r, interpolated, part, total);
-    if (rc != SONAR_OK) return rc;
-    rc = o.give(magnitude ? magnitude + s0 * K : nullptr, scratch, (size_t)nf * (size_t)K * 8);
-    if (rc != SONAR_OK) return rc;
-  }
-  return o.finish();
+    const int erc = estimate_rows(c, rows, nf, K, window_size, sample_rate, num_harmonics, r, interpolated, part, total);
+    return erc != SONAR_OK ? erc : o.give(magnitude ? magnitude + s0 * K : nullptr, rows, (size_t)nf * (size_t)K * 8);
+  });
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 }  // extern "C"

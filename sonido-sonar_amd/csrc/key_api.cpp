@@ -138,27 +138,17 @@ int launch_rows(sonar_ctx* c, const sonar::KeyArgs& a) {
   return SONAR_OK;
 }
 
-// the chromagram on the device and the non-finite flag
+// the chromagram on the device and the non-finite flag (the call's status word)
 void stage_input(Staging& o, const double* chroma, int64_t F, int32_t dim, sonar::KeyArgs& a) {
   a.chroma = o.in("in", chroma, (size_t)F * (size_t)dim);
-  a.nonfinite = o.tmp<int32_t>("flag", 1);
+  a.nonfinite = o.flag();
 }
 
-// after the allocations: the one out-of-memory report, the input copy and the zeroed flag, all queued
-int begin(sonar_ctx* c, Staging& o, int32_t* flag) {
-  const int rc = o.ready("device allocation failed");
-  if (rc != SONAR_OK) return rc;
-  HIP_TRY(c, hipMemsetAsync(flag, 0, 4, c->stream));
-  return SONAR_OK;
-}
-
-// copies the host-mode outputs back, waits, and reports a non-finite input
-int finish(sonar_ctx* c, Staging& o, const int32_t* flag) {
-  int32_t bad = 0;
-  HIP_TRY(c, hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, c->stream));
+// the end of an entry: the outputs and the flag are back; a non-finite input is reported
+int done(sonar_ctx* c, Staging& o) {
   const int rc = o.finish();
   if (rc != SONAR_OK) return rc;
-  if (bad)
+  if (o.flags())
     return fail(c, SONAR_ERR_UNSUPPORTED,
                 "key estimation: a non-finite chroma value is not reproduced (a NaN score leaves the order of "
                 "sort.Slice undefined)");
@@ -223,13 +213,13 @@ int sonar_key_frames(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim,
   a.F = F;
   frame_outs(o, {key, mode, known, confidence, strength, clarity, ambiguity, tonality, scores, candidates, processed},
              (size_t)F, a, a);
-  rc = begin(c, o, a.nonfinite);
+  rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   hipEvent_t tend = timed_begin(c, c->stream);
   rc = launch_rows(c, a);
   if (rc != SONAR_OK) return rc;
   timed_end(c, c->stream, tend);
-  return finish(c, o, a.nonfinite);
+  return done(c, o);
 }
 
 int sonar_key_sequence(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, const sonar_key_params* params,
@@ -271,7 +261,7 @@ int sonar_key_sequence(sonar_ctx* c, const double* chroma, int64_t F, int32_t di
   int64_t* dnmod = o.out("nmod", n_modulations, 1);
   int32_t* wcode = want_mod && nw ? o.tmp<int32_t>("wcode", (size_t)nw) : nullptr;
   double* wconf = want_mod && nw ? o.tmp<double>("wconf", (size_t)nw) : nullptr;
-  rc = begin(c, o, base.nonfinite);
+  rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   hipEvent_t tend = timed_begin(c, s);
   if (sonar::launch_key_colsum(din, F, dim, avg, s) != 0) return fail(c, SONAR_ERR_DEVICE, "key average launch failed");
@@ -301,7 +291,7 @@ int sonar_key_sequence(sonar_ctx* c, const double* chroma, int64_t F, int32_t di
     }
   }
   timed_end(c, s, tend);
-  return finish(c, o, base.nonfinite);
+  return done(c, o);
 }
 
 int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, const sonar_key_params* params,
@@ -318,10 +308,7 @@ int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, 
   Staging o{c, "key.", device_ptrs != 0};
   if (F == 0) {                                             // :924-926, :963-965
     const int32_t none = -1;
-    if (global_code) {
-      if (o.dev) HIP_TRY(c, hipMemcpyAsync(global_code, &none, 4, hipMemcpyHostToDevice, s));
-      else *global_code = none;
-    }
+    if ((rc = o.put(global_code, &none, 4)) != SONAR_OK) return rc;
     return o.zero({{global_confidence, 8}, {global_strength, 8}, {votes, 24 * 8}, {n_transitions, 8}});
   }
   sonar::KeyArgs a{};
@@ -350,7 +337,7 @@ int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, 
   k.tconf = o.out("tconf", t_confidence, cap);
   k.type = o.out("ttype", t_type, cap);
   k.count = o.out("ntrans", n_transitions, 1);
-  rc = begin(c, o, a.nonfinite);
+  rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   hipEvent_t tend = timed_begin(c, s);
   rc = launch_rows(c, a);
@@ -362,7 +349,7 @@ int sonar_key_batch(sonar_ctx* c, const double* chroma, int64_t F, int32_t dim, 
     if (sonar::launch_key_compact(k, s) != 0) return fail(c, SONAR_ERR_DEVICE, "key progression launch failed");
   }
   timed_end(c, s, tend);
-  return finish(c, o, a.nonfinite);
+  return done(c, o);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // and TempoEstimation (tempo_estimation.go) over SpectralFlux (spectral/spectral_flux.go) and
 // Envelope.ComputeRMS (temporal/envelope.go).  The host side: the argument checks, Go's truncating
 // conversions (minIntervalFrames, the 100 ms frame, the lag range), the staged arrays of each entry
-// (staging.h), the chunk loop of the flux detector over the float64 transform with no window, and the
+// (staging.h), the flux detector over the chunked walk of the float64 transform with no window, and the
 // short serial tails that act on a few values per second of audio: combineOnsets, the interval
 // histogram and the peak search over the 30-odd lags the reference reads.  The kernels are
 // onset_kernels.hip's.
@@ -16,6 +16,7 @@
 #include "ctx.h"
 #include "go_math.h"
 #include "kernels.h"
+#include "magnitude_walk.h"
 #include "staging.h"
 
 using sonar::detail::fail;
@@ -70,11 +71,11 @@ std::string tagged(const char* tag, const char* name) { return std::string(tag) 
 // DetectOnsets (:26-56) on device samples: the spectrogram in chunks through a bounded scratch, the
 // flux of every chunk with the last row of the chunk before it carried across, then the peaks
 struct FluxDetector {
-  sonar_fp_cfg cfg;
-  int64_t n = 0, F = 0, cf = 0, width = 0;
-  int32_t W = 0, H = 0, K = 0, mif = 0;
+  sonar::detail::MagnitudeWalk walk;
+  int64_t n = 0, width = 0;
+  int32_t mif = 0;
   double threshold = 0.0;
-  double *flux = nullptr, *scratch = nullptr;
+  double* flux = nullptr;
   uint64_t* mask = nullptr;
   int64_t *onsets = nullptr, *dcount = nullptr;
 
@@ -82,24 +83,21 @@ struct FluxDetector {
   int plan(int64_t samples, bool have_pcm, int32_t sample_rate, int32_t window_size, int32_t hop_size, double thr,
            double min_interval, std::string& msg) {
     n = samples;
-    W = window_size ? window_size : SONAR_ONSET_WINDOW;
-    H = hop_size ? hop_size : SONAR_ONSET_HOP;
     threshold = thr;
     // a nil window is no window (stft.go:112): the rectangular table is all ones, x * 1.0 is x
-    sonar::detail::magnitude_fp_cfg(sample_rate, W, H, SONAR_WIN_RECTANGULAR, &cfg);
-    int rc = sonar::detail::fp_check(&cfg, n, have_pcm, &F, &msg);
+    int rc = walk.plan(sample_rate, window_size ? window_size : SONAR_ONSET_WINDOW, hop_size ? hop_size : SONAR_ONSET_HOP,
+                       SONAR_WIN_RECTANGULAR, n, have_pcm, &msg);
     if (rc != SONAR_OK) return rc;
-    K = W / 2 + 1;
-    rc = min_interval_frames(min_interval, sample_rate, H, &mif, msg);
+    rc = min_interval_frames(min_interval, sample_rate, walk.H, &mif, msg);
     if (rc != SONAR_OK) return rc;
-    cf = sonar::detail::magnitude_chunk_frames(W);
-    width = peaks_width(F - 1);
+    width = peaks_width(walk.F - 1);
     return SONAR_OK;
   }
   void alloc(Staging& o, const char* tag, double* user_flux, int64_t* user_onsets) {
+    const int64_t F = walk.F;
     const size_t nflux = (size_t)std::max<int64_t>(F - 1, 1);
     flux = user_flux ? o.out(tagged(tag, "flux").c_str(), user_flux, nflux) : o.tmp<double>(tagged(tag, "flux").c_str(), nflux);
-    scratch = o.tmp<double>(tagged(tag, "chunk").c_str(), ((size_t)std::min(cf, F) + 1) * (size_t)K);
+    walk.alloc(o, 1, tagged(tag, "chunk").c_str());   // one row before the chunk's: the last row of the chunk before it
     mask = o.tmp<uint64_t>(tagged(tag, "mask").c_str(), (size_t)std::max<int64_t>(sonar::onset_mask_words(F - 1), 1));
     const size_t slots = (size_t)std::max<int64_t>(width, 1);
     onsets = user_onsets ? o.out(tagged(tag, "onsets").c_str(), user_onsets, slots)
@@ -107,28 +105,23 @@ struct FluxDetector {
     dcount = o.tmp<int64_t>(tagged(tag, "count").c_str(), 1);
   }
   int run(sonar_ctx* c, Staging& o, const double* dx, double* user_magnitude) {
-    double* rows = scratch + K;   // slot 0 holds the row before the chunk
-    for (int64_t s0 = 0; s0 < F; s0 += cf) {
-      const int64_t nf = std::min(cf, F - s0);
-      sonar_fp_out fo;
-      std::memset(&fo, 0, sizeof fo);
-      fo.magnitude = rows;
-      // Go's truncating frame count gives a signal with n in (W - H, W) one frame, left all zero
-      // (stft.go:59, :140): the transform sees the samples there are, never more
-      int rc = sonar::detail::fingerprint_impl(c, dx + s0 * H, std::min((nf - 1) * H + W, n - s0 * H), &cfg, &fo, true);
-      if (rc != SONAR_OK) return rc;
+    const int64_t F = walk.F, K = walk.K, cf = walk.chunk_frames;
+    double* carried = walk.rows - K;
+    const int rc = walk.each(c, dx, n, false, [&](const double* rows, int64_t s0, int64_t nf) -> int {
       hipEvent_t tend = timed_begin(c, c->stream);
       const int lrc = s0 == 0 ? sonar::launch_onset_flux(rows, nf, K, false, flux, c->stream)
-                              : sonar::launch_onset_flux(scratch, nf + 1, K, false, flux + (s0 - 1), c->stream);
+                              : sonar::launch_onset_flux(carried, nf + 1, K, false, flux + (s0 - 1), c->stream);
       if (lrc != 0) return fail(c, SONAR_ERR_DEVICE, "spectral flux launch failed");
       timed_end(c, c->stream, tend);
-      rc = o.give(user_magnitude ? user_magnitude + s0 * K : nullptr, rows, (size_t)nf * (size_t)K * 8);
-      if (rc != SONAR_OK) return rc;
+      const int grc = o.give(user_magnitude ? user_magnitude + s0 * K : nullptr, rows, (size_t)nf * (size_t)K * 8);
+      if (grc != SONAR_OK) return grc;
       if (s0 + cf < F)
-        HIP_TRY(c, hipMemcpyAsync(scratch, rows + (nf - 1) * K, (size_t)K * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
+        HIP_TRY(c, hipMemcpyAsync(carried, rows + (nf - 1) * K, (size_t)K * 8, hipMemcpyDeviceToDevice, c->stream));
+      return SONAR_OK;
+    });
+    if (rc != SONAR_OK) return rc;
     // onset sample = index in the flux array * hop (:50-53)
-    return pick(c, flux, F - 1, threshold, mif, H, mask, onsets, width, dcount);
+    return pick(c, flux, F - 1, threshold, mif, walk.H, mask, onsets, width, dcount);
   }
 };
 
@@ -266,7 +259,7 @@ struct AcEstimator {
     }
   }
   // waits for the stream once, for the window's values
-  int run(sonar_ctx* c, const double* dx, double* tempo, int64_t* best_lag) {
+  int run(sonar_ctx* c, Staging& o, const double* dx, double* tempo, int64_t* best_lag) {
     *tempo = 0.0;
     *best_lag = 0;
     if (p.L < 10) return SONAR_OK;   // :62-64
@@ -281,9 +274,9 @@ struct AcEstimator {
     if (sonar::launch_onset_autocorr(env, p.L, wlo, nwin + 1, true, narrow, s) != 0)
       return fail(c, SONAR_ERR_DEVICE, "tempo: autocorrelation launch failed");
     timed_end(c, s, tend);
-    std::vector<double> h((size_t)nwin + 1);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), narrow, h.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    const double* h = o.back(narrow, (size_t)nwin + 1);
+    const int rc = o.fetch();
+    if (rc != SONAR_OK) return rc;
     // the in-place normalisation (:143-147): autocorr[0] becomes its own quotient, the rest is divided by that
     const double a0 = h[0];
     const bool norm = a0 > 0.0;
@@ -305,14 +298,6 @@ struct AcEstimator {
   }
 };
 
-// a host value into an output of the caller's, whichever kind it is
-int put(sonar_ctx* c, void* user, const void* host, size_t bytes, bool dev) {
-  if (!user || bytes == 0) return SONAR_OK;
-  if (dev) HIP_TRY(c, hipMemcpy(user, host, bytes, hipMemcpyHostToDevice));
-  else std::memcpy(user, host, bytes);
-  return SONAR_OK;
-}
-
 // DetectOnsetsComplex (:123-146) on device samples: both detectors, then combineOnsets on the host
 // after one copy of the two lists.  rc is the flux detector's plan error, which ends the call (:135-137).
 int complex_onsets(sonar_ctx* c, Staging& o, const double* dx, FluxDetector& fd, EnergyDetector& ed,
@@ -320,15 +305,12 @@ int complex_onsets(sonar_ctx* c, Staging& o, const double* dx, FluxDetector& fd,
   int rc = fd.run(c, o, dx, nullptr);
   if (rc == SONAR_OK) rc = ed.run(c, dx);
   if (rc != SONAR_OK) return rc;
-  std::vector<int64_t> hf((size_t)fd.width + 1), he((size_t)ed.width + 1);   // the count, then the list
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(hf.data(), fd.dcount, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(he.data(), ed.dcount, 8, hipMemcpyDeviceToHost, s));
-  if (fd.width) HIP_TRY(c, hipMemcpyAsync(hf.data() + 1, fd.onsets, (size_t)fd.width * 8, hipMemcpyDeviceToHost, s));
-  if (ed.width) HIP_TRY(c, hipMemcpyAsync(he.data() + 1, ed.onsets, (size_t)ed.width * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  const int64_t nf = std::min(hf[0], fd.width), ne = std::min(he[0], ed.width);
-  *out = combine(hf.data() + 1, nf, he.data() + 1, ne, (int64_t)(kComplexMinInterval * (double)sample_rate));
+  const int64_t *cf = o.back(fd.dcount, 1), *ce = o.back(ed.dcount, 1);
+  const int64_t *hf = o.back(fd.onsets, (size_t)fd.width), *he = o.back(ed.onsets, (size_t)ed.width);
+  rc = o.fetch();
+  if (rc != SONAR_OK) return rc;
+  *out = combine(hf, std::min(*cf, fd.width), he, std::min(*ce, ed.width),
+                 (int64_t)(kComplexMinInterval * (double)sample_rate));
   return SONAR_OK;
 }
 
@@ -422,12 +404,11 @@ int sonar_onset_peaks(sonar_ctx* c, const double* curve, int64_t n, double thres
   int64_t* di = o.out("index", index, (size_t)width);
   uint64_t* mask = o.tmp<uint64_t>("mask", (size_t)sonar::onset_mask_words(n));
   int64_t* dc = o.tmp<int64_t>("count", 1);
-  if (dc) o.d2h.push_back({count, dc, 8});
+  o.host_out(count, dc, 1);
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   rc = pick(c, dv, n, threshold, mif, 1, mask, di, width, dc);
-  if (rc != SONAR_OK) return rc;
-  return o.finish();
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 int sonar_onset_adaptive_threshold(sonar_ctx* c, const double* curve, int64_t n, double* value, int32_t device_ptrs) {
@@ -462,18 +443,17 @@ int sonar_onsets_flux(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample
   std::string msg;
   int rc = fd.plan(n, pcm != nullptr, sample_rate, window_size, hop_size, threshold, min_interval, msg);
   if (rc != SONAR_OK) return fail(c, rc, msg);
-  if (frames) *frames = fd.F;
+  if (frames) *frames = fd.walk.F;
   if (fd.width > 0 && !onsets) return fail(c, SONAR_ERR_INVALID, "onsets: null onsets pointer");
   HIP_TRY(c, hipSetDevice(c->device));
   Staging o{c, "onsets.", device_ptrs != 0};
   const double* dx = o.in("pcm", pcm, (size_t)n);
-  fd.alloc(o, "f.", fd.F > 1 ? flux : nullptr, fd.width > 0 ? onsets : nullptr);
-  if (fd.dcount) o.d2h.push_back({count, fd.dcount, 8});
+  fd.alloc(o, "f.", fd.walk.F > 1 ? flux : nullptr, fd.width > 0 ? onsets : nullptr);
+  o.host_out(count, fd.dcount, 1);
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   rc = fd.run(c, o, dx, magnitude);
-  if (rc != SONAR_OK) return rc;
-  return o.finish();
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 int sonar_onsets_energy(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, int32_t frame_size,
@@ -497,12 +477,11 @@ int sonar_onsets_energy(sonar_ctx* c, const double* pcm, int64_t n, int32_t samp
   Staging o{c, "onsets.", device_ptrs != 0};
   const double* dx = o.in("pcm", pcm, (size_t)n);
   ed.alloc(o, "e.", ed.ncurve > 0 ? curve : nullptr, ed.width > 0 ? onsets : nullptr);
-  if (ed.dcount) o.d2h.push_back({count, ed.dcount, 8});
+  o.host_out(count, ed.dcount, 1);
   rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   rc = ed.run(c, dx);
-  if (rc != SONAR_OK) return rc;
-  return o.finish();
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 int sonar_onsets_complex(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, int64_t* onsets,
@@ -534,7 +513,8 @@ int sonar_onsets_complex(sonar_ctx* c, const double* pcm, int64_t n, int32_t sam
   if (rc != SONAR_OK) return rc;
   *count = (int64_t)kept.size();
   kept.resize((size_t)width, 0);                             // the slots past count are 0
-  rc = put(c, onsets, kept.data(), (size_t)width * 8, device_ptrs != 0);
+  rc = o.put(onsets, kept.data(), (size_t)width * 8);
+  if (rc == SONAR_OK) rc = o.settle();
   if (rc != SONAR_OK) return rc;
   const double duration = (double)n / (double)sample_rate;   // ComputeOnsetDensity (:191-196)
   if (density) *density = duration == 0 ? 0.0 : (double)*count / duration;
@@ -576,24 +556,20 @@ int sonar_tempo_autocorrelation(sonar_ctx* c, const double* pcm, int64_t n, int3
   if (sample_rate <= 0) return fail(c, SONAR_ERR_UNSUPPORTED, "tempo: sample_rate <= 0 is not reproduced");
   if (n > 0 && !pcm) return fail(c, SONAR_ERR_INVALID, "tempo: null pcm pointer");
   HIP_TRY(c, hipSetDevice(c->device));
-  const bool dev = device_ptrs != 0;
   AcEstimator ac;
   ac.plan(n, sample_rate);
   if (n_autocorr) *n_autocorr = ac.p.nac;
-  Staging o{c, "tempo.", dev};
+  Staging o{c, "tempo.", device_ptrs != 0};
   const double* dx = ac.p.L >= 10 ? o.in("pcm", pcm, (size_t)n) : nullptr;
   ac.alloc(o, "a.", autocorr);
   int rc = o.ready("device allocation failed");
   if (rc != SONAR_OK) return rc;
   double t = 0.0;
   int64_t lag = 0;
-  rc = ac.run(c, dx, &t, &lag);
-  if (rc != SONAR_OK) return rc;
-  rc = o.finish();
-  if (rc != SONAR_OK) return rc;
-  rc = put(c, tempo, &t, 8, dev);
-  if (rc == SONAR_OK) rc = put(c, best_lag, &lag, 8, dev);
-  return rc;
+  rc = ac.run(c, o, dx, &t, &lag);
+  if (rc == SONAR_OK) rc = o.put(tempo, &t, 8);
+  if (rc == SONAR_OK) rc = o.put(best_lag, &lag, 8);
+  return rc != SONAR_OK ? rc : o.finish();
 }
 
 int sonar_tempo(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate, sonar_tempo_result* result,
@@ -637,7 +613,7 @@ int sonar_tempo(sonar_ctx* c, const double* pcm, int64_t n, int32_t sample_rate,
     result->onset_tempo = tempo_from_onsets(kept.data(), (int64_t)kept.size(), sample_rate, nullptr);
   }
   result->onset_error = onset_rc;
-  rc = ac.run(c, dx, &result->autocorr_tempo, &result->best_lag);
+  rc = ac.run(c, o, dx, &result->autocorr_tempo, &result->best_lag);
   if (rc != SONAR_OK) return rc;
   rc = o.finish();
   if (rc != SONAR_OK) return rc;

@@ -310,21 +310,15 @@ int sonar_pitch_detect(sonar_ctx* c, const double* pcm, int64_t n, const sonar_p
   if (frames) *frames = F;
   if (F == 0) return SONAR_OK;
   double* outs[9] = {pitch, confidence, voicing, periodicity, clarity, strength, salience, stability, f0_multiple};
-  if (!device_ptrs) {
-    rc = sonar_pitch_track(p, F, rp.data(), rc_.data(), nc.data(), sc.data(), pitch, confidence, voicing, periodicity,
-                           clarity, strength, salience, stability, f0_multiple);
-    return rc == SONAR_OK ? SONAR_OK : fail(c, rc, "pitch detection: tracker arguments");
-  }
   std::vector<double> h((size_t)F * 9);
   double* hp[9];
   for (int k = 0; k < 9; ++k) hp[k] = h.data() + (size_t)k * F;
   rc = sonar_pitch_track(p, F, rp.data(), rc_.data(), nc.data(), sc.data(), hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6],
                          hp[7], hp[8]);
   if (rc != SONAR_OK) return fail(c, rc, "pitch detection: tracker arguments");
-  for (int k = 0; k < 9; ++k)
-    if (outs[k]) HIP_TRY(c, hipMemcpyAsync(outs[k], hp[k], (size_t)F * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SONAR_OK;
+  Staging o{c, "pitch.", device_ptrs != 0};
+  for (int k = 0; k < 9 && rc == SONAR_OK; ++k) rc = o.put(outs[k], hp[k], (size_t)F * 8);
+  return rc != SONAR_OK || !o.dev ? rc : o.finish();
 }
 
 int sonar_pitch_stability(const double* pitch, int64_t n, int32_t sample_rate, int32_t hop_size, double* out7,

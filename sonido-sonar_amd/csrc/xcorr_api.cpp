@@ -105,13 +105,12 @@ int xcorr_run(sonar_ctx* c, const double* a, int64_t na, const double* b, int64_
   }
   if (rc != 0) return fail(c, SONAR_ERR_DEVICE, "correlation launch failed");
   timed_end(c, s, tend);
-  std::vector<double> hc((size_t)nl);
-  HIP_TRY(c, hipMemcpyAsync(hc.data(), dc, nl * 8, hipMemcpyDeviceToHost, s));
+  const double* hc = o.back(dc, (size_t)nl);
   const int frc = o.finish();
   if (frc != SONAR_OK) return frc;
-  if (corr && !o.dev) std::memcpy(corr, hc.data(), nl * 8);
+  if (corr && !o.dev) std::memcpy(corr, hc, nl * 8);
   if (metrics) {
-    sonar::detail::ncc_metrics_host(hc.data(), L, na, nb, metrics);   // [0..9], as sonar_ncc
+    sonar::detail::ncc_metrics_host(hc, L, na, nb, metrics);   // [0..9], as sonar_ncc
     metrics[10] = (double)method;
     metrics[11] = (double)corr_type;
   }

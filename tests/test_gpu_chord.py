@@ -380,3 +380,48 @@ def test_detect_unsupported_and_errors(ctx):
     _raises(sonar.ERR_UNSUPPORTED, "temporal_window", ctx.chord_detect, pcm, sr, 2048, 512,
             sonar.chord_params(temporal_window=65))
     _raises(sonar.ERR_INVALID, "positive", ctx.chord_detect, pcm, sr, 2048, 0)
+
+
+def test_detect_across_its_chunk_seam(ctx):
+    """Frames of 2048 samples at hop 1 go through the magnitude scratch 2048 at a time: 2050 frames are a
+    chunk of 2048 and one of 2.  The profiles on both sides of the seam are those of a call that sees the same
+    frames in one chunk, bit for bit, and the chords are those of the sequence over the returned profiles."""
+    frame_len, hop, sr, n = 2048, 1, 44100, 4097
+    pcm = _signal(n, sr)
+    p = sonar.chord_params()
+    got = ctx.chord_detect(pcm, sr, frame_len, hop, p)
+    assert got["hpcp"].shape == (2050, 12)
+    part = ctx.chord_detect(pcm[2040:2040 + 2057], sr, frame_len, hop, p)
+    assert part["hpcp"].shape == (10, 12) and _same(got["hpcp"][2040:2050], part["hpcp"])
+    assert np.any(got["hpcp"][2046:2050] != 0.0)
+    want = ctx.chord_sequence(got["hpcp"], p)
+    for n_ in sonar.CHORD_FIELDS:
+        assert np.array_equal(got[n_], want[n_]) if got[n_].dtype == np.int32 else _same(got[n_], want[n_]), n_
+
+
+def test_flag_word_texts(ctx):
+    """What the device's status word means, code and whole text, at one or two rows: the three flags of the row
+    entries and the two of the progression."""
+    def exact(code, text, fn, *a):
+        with pytest.raises(SonarError) as e:
+            fn(*a)
+        assert (e.value.code, e.value.msg) == (code, text)
+    P = sonar.chord_params
+    rows = np.array(K.rows_b()[:2])
+    nan_row = rows.copy()
+    nan_row[1, 3] = np.nan
+    nonfinite = ("chord detection: a non-finite chroma value or bass confidence is not reproduced (a NaN confidence "
+                 "leaves the order of sort.Slice undefined)")
+    for fn in (ctx.chord_frames, ctx.chord_sequence):
+        exact(sonar.ERR_INVALID, "chord detection: a bass note outside 0..11", fn, rows, P(), np.array([0, 12]),
+              np.array([0.5, 0.5]))
+        exact(sonar.ERR_UNSUPPORTED, nonfinite, fn, nan_row, P())
+        exact(sonar.ERR_UNSUPPORTED, nonfinite, fn, rows[:1], P(), np.array([3]), np.array([np.inf]))
+    # a frame without candidates after one with, under a negative window: history[1:] of an empty history
+    gap = np.array([K.rows_b()[0], [0.0] * 12])
+    p = P(temporal_window=-1)
+    with pytest.raises(IndexError, match=r"slice bounds out of range \[1:0\]"):
+        R.sequence(gap, {n: getattr(p, n) for n, _ in p._fields_}, None, None)
+    exact(sonar.ERR_PANIC, "runtime error: slice bounds out of range [1:0]", ctx.chord_sequence, gap, p)
+    exact(sonar.ERR_UNSUPPORTED, "chord progression: a quality code outside 0..31", ctx.chord_progression, [0, 32], [0.5, 0.5])
+    exact(sonar.ERR_UNSUPPORTED, "chord progression: a non-finite confidence", ctx.chord_progression, [0, 1], [0.5, np.nan])
