@@ -1116,7 +1116,8 @@ typedef struct {
 } sonar_formant_frame;
 
 int64_t sonar_formant_frame_count(int64_t n, int32_t sample_rate, int32_t frame_size, int32_t hop_size);
-/* lpc_coeffs (nullable): frames x (order+1) a[0..p], a[0] = 1; reflection (nullable): frames x order */
+/* lpc_coeffs (nullable): frames x (order+1) a[0..p], a[0] = 1; reflection (nullable): frames x order;
+ * the rows of a frame with status != 0 are zero */
 int sonar_formants(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t sample_rate, int32_t frame_size,
                    int32_t hop_size, sonar_formant_frame* out, double* lpc_coeffs, double* reflection,
                    int32_t device_ptrs);

@@ -68,8 +68,15 @@ __global__ __launch_bounds__(256, FMT_MIN_BLOCKS) void formant_kernel(const doub
   const double* sig = pcm + f * hop;
   sonar_formant_frame* o = out + f;
 
+  // a rejected frame's coefficient rows are zero, as Go's unassigned slices are: the caller's device
+  // buffers are reused (or its own, with device_ptrs) and would otherwise keep an earlier call's rows
+  auto zero_rows = [&]() {
+    if (coeffs) for (int i = tid; i <= p; i += 256) coeffs[f * (p + 1) + i] = 0.0;
+    if (refl) for (int i = tid; i < p; i += 256) refl[f * p + i] = 0.0;
+  };
   if (!frame_ok_len) {                              // len(frame) < windowSize (format.go:86-88)
     if (tid == 0) { clear_record(o, 1, p); o->gain = 0.0; o->residual_energy = 0.0; }
+    zero_rows();
     return;
   }
   #pragma unroll 8
@@ -135,6 +142,7 @@ __global__ __launch_bounds__(256, FMT_MIN_BLOCKS) void formant_kernel(const doub
   const double E = red[1];
   if (status != 0) {
     if (tid == 0) clear_record(o, status, p);
+    zero_rows();
     return;
   }
   if (coeffs) for (int i = tid; i <= p; i += 256) coeffs[f * (p + 1) + i] = a[i];

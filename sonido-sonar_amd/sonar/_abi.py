@@ -470,7 +470,8 @@ def lib():
 def _formant_dict(recs, F):
     a = np.ctypeslib.as_array(recs)[:F] if F else np.zeros(0, dtype=np.dtype(FormantFrame))
     return {k: np.array(a[k]) for k in ("status", "n_formants", "frequency", "bandwidth", "amplitude", "confidence",
-                                        "vocal_tract_length", "quality", "gain", "residual_energy", "stable")}
+                                        "vocal_tract_length", "quality", "gain", "residual_energy", "stable",
+                                        "lpc_order")}
 
 
 def abi_version():
