@@ -1714,6 +1714,192 @@ int sonar_pitch_detect(sonar_ctx* ctx, const double* pcm, int64_t n, const sonar
 int sonar_pitch_stability(const double* pitch, int64_t n, int32_t sample_rate, int32_t hop_size, double* out7,
                           int32_t* empty);
 
+/* ---- HarmonicRatioAnalyzer in full (algorithms/tonal/harmonic_ratio.go): every method of AnalyzeFrame's
+ * switch (:228-243), its post-processing and temporal tracking, AnalyzeSequence and the helpers.
+ * Everything is float64.  sonar_extract_music_features keeps writing its harmonic_ratio row as zeros
+ * (SURVEY.md F7); these entries are the analyzer itself. ------------------------------------------ */
+enum {                             /* HarmonicRatioMethod (:17-24), Go's values; every other value is HNR, the
+                                      switch's default case (:241) */
+  SONAR_HRATIO_HNR = 0,
+  SONAR_HRATIO_ACF = 1,
+  SONAR_HRATIO_HPS = 2,
+  SONAR_HRATIO_COMB = 3,           /* analyzeComb is analyzeHNR (:457-461) */
+  SONAR_HRATIO_SPECTRAL = 4,
+  SONAR_HRATIO_YIN = 5
+};
+enum {                             /* NoiseFloorMethod's strings (:633-642); Go maps every other string to
+                                      "percentile", which the bindings do before they fill the field, and so
+                                      does the library with every other value */
+  SONAR_HRATIO_NOISE_MEDIAN = 0,
+  SONAR_HRATIO_NOISE_PERCENTILE = 1,
+  SONAR_HRATIO_NOISE_MINIMUM = 2
+};
+enum {                             /* ClassifyHarmonicRatio's categories (:1130-1142) */
+  SONAR_HRATIO_VERY_LOW = 0, SONAR_HRATIO_LOW = 1, SONAR_HRATIO_MEDIUM = 2, SONAR_HRATIO_HIGH = 3,
+  SONAR_HRATIO_VERY_HIGH = 4
+};
+#define SONAR_HRATIO_MAX_HARMONICS 64
+/* HarmonicRatioParams (:27-57) field for field, and autocorr_max_lag: the argument of the analyzer's
+ * NewAutoCorrelation, 2048 in NewHarmonicRatioAnalyzer (:157) and WindowSize in ...WithParams (:171).
+ * The reference never reads use_freq_weighting, use_psychoacoustic_mask and adaptive_threshold, and reads
+ * hop_size nowhere either: the entries here use it as the frame step of a signal, which in Go is the
+ * caller's slicing.  The library ignores the never-read fields as well.  min_peak_height is the height of
+ * the analyzer's peak detector, NewSpectralPeaks(sample_rate, min_peak_height, 20.0, 100): 0.001 in
+ * NewHarmonicRatioAnalyzer, which hard-codes it (:155), and params.MinPeakHeight in ...WithParams (:169);
+ * nothing else reads the field. */
+typedef struct sonar_hratio_params {
+  int32_t method;                  /* SONAR_HRATIO_* */
+  int32_t sample_rate;
+  int32_t window_size;
+  int32_t hop_size;                /* never read by the reference; the frame step here */
+  double min_freq, max_freq;
+  int32_t max_harmonics;
+  double harmonic_tolerance;
+  double min_peak_height;
+  int32_t peak_detection_width;
+  int32_t spectral_smoothing_len;
+  int32_t noise_floor_method;      /* SONAR_HRATIO_NOISE_* */
+  double noise_floor_percentile;
+  int32_t noise_floor_smoothing_len;
+  int32_t use_temporal_smoothing;  /* 0 / 1 */
+  int32_t temporal_smoothing_len;
+  int32_t use_freq_weighting;      /* never read */
+  int32_t use_psychoacoustic_mask; /* never read */
+  int32_t adaptive_threshold;      /* never read */
+  int32_t autocorr_max_lag;
+} sonar_hratio_params;
+
+/* NewHarmonicRatioAnalyzer(sample_rate) (:130-161): HNR, 2048 / 512, 80-8000 Hz, 20 harmonics, tolerance
+ * 0.1, height 0.001, width 3, smoothing 5, "percentile" 0.1 smoothed over 10, temporal smoothing on over 5,
+ * the three unread switches off, autocorr_max_lag 2048. */
+void sonar_hratio_params_default(sonar_hratio_params* p, int32_t sample_rate);
+
+/* The parameter checks of the entries below, without a device.  SONAR_OK or a negative SONAR_ERR_*:
+ *   NULL params -> SONAR_ERR_INVALID;
+ *   sample_rate < 1 or hop_size < 1 -> SONAR_ERR_INVALID;
+ *   min_freq, max_freq, harmonic_tolerance or min_peak_height not finite -> SONAR_ERR_INVALID (a documented
+ *     narrowing: Go would convert an infinity or a NaN to int);
+ *   noise_floor_method percentile (or unknown) with a NaN noise_floor_percentile -> SONAR_ERR_PANIC "stat:
+ *     percentile out of bounds" (common.Percentile's own range test lets a NaN through to gonum, HNR and
+ *     Comb included: computeSpectrum estimates the floor under every method);
+ *   method HPS with int(min_freq W / sr) < 0 and a scan that starts (int(max_freq W / sr) above it) ->
+ *     SONAR_ERR_PANIC "runtime error: index out of range [-N]" (hps[i] :434);
+ *   temporal_smoothing_len < 0 -> SONAR_ERR_PANIC "runtime error: slice bounds out of range [a:b]" with
+ *     a = 1 + 2 |len|, b = 1 (hrHistory[len - maxHistory:] :996, at the first frame), from
+ *     sonar_hratio_track and sonar_hratio only: the per-frame entries never reach that line;
+ *   window_size not a power of two in [64, 2048] (the LDS tile of the transform, go-dsp's radix-2 branch),
+ *     max_harmonics > 64, autocorr_max_lag < window_size - 1 (fewer than all lags; both constructors give
+ *     all of them at a supported window), |min_freq| or |max_freq| times W / sr beyond 2^31 ->
+ *     SONAR_ERR_UNSUPPORTED.
+ * A frame-size mismatch (:213) cannot occur: the entries slice the frames themselves. */
+int sonar_hratio_check(const sonar_hratio_params* p);
+
+/* Everything AnalyzeFrame does after the transform for the methods HNR, COMB (which is HNR), HPS and
+ * SPECTRAL, on F rows of K = W / 2 unsmoothed magnitudes |X| (computeSpectrum's hra.magnitude before :286)
+ * and, optionally, their phases.  Host pointers, or device pointers for mag, phase and every output when
+ * device_ptrs is set.  Every output may be NULL and then costs nothing.  Per frame:
+ *   harmonic_ratio (raw, before postProcessResult's smoothing), harmonic_energy, noise_energy,
+ *   total_energy, f0, f0_confidence, snr, periodicity, harmonicity, voicing, roughness, num_harmonics;
+ *   h_bin, h_freq, h_amp, h_phase: F x max_harmonics, the result's SpectralPeaks (BinIndex, Frequency,
+ *   Magnitude, Phase), which HNR also copies to HarmonicFrequencies / Amplitudes / Phases; slots past
+ *   num_harmonics are -1 for h_bin and 0 for the rest; h_phase is 0 when phase is NULL;
+ *   noise_floor: F x K.
+ * Fields a method leaves unset in Go's result are 0: HPS sets harmonic_ratio, f0, the peaks and
+ * num_harmonics; SPECTRAL adds the three energies; HNR sets all of them.
+ * Quirks of the reference kept here:
+ *  - MovingAverage (common/math.go:140-166) is a trailing window: entry i < L averages 0..i, the others
+ *    the L entries ending at i, sums in j order; L > K or L <= 0 returns the input.  Smoothing runs only
+ *    for a length above 1 (:286, :645).
+ *  - The noise floor (:650-705) of bin i looks at [max(0, i - 10), min(K, i + 10)), 10 to 20 values.
+ *    common.Percentile is gonum's stat.Quantile(p, stat.Empirical, sorted, nil): the first sorted value
+ *    whose count reaches p n (x[0] at p = 0); "median" is that at 0.5, not a mean of two.  gonum is restated
+ *    from its published rule, parity unpinned.  A percentile outside [0, 1] gives a floor of zeros
+ *    (math.go:39) and an SNR of 60.
+ *  - detectFundamentalFrequency (:546-563) walks DetectPeaks' output, sorted by magnitude descending, for
+ *    its "lowest significant peak": f0 is the strongest of the 100 strongest peaks at or above min_freq,
+ *    else the strongest of all; f0_confidence is that peak's magnitude, not a value in [0, 1].  No peak:
+ *    f0 0, no harmonics, harmonic_energy 0 and harmonic_ratio -Inf when there is noise energy.
+ *  - The detector runs on the K smoothed magnitudes as sonar_spectral_peaks defines it, with
+ *    DetectPeaks(mag, W): equal magnitudes in ascending bin order, also for estimateF0FromPeaks' second
+ *    sort.  At a power-of-two W, i sr / W (freqBins :195) and i (sr / W) (the detector) are the same double,
+ *    because sr / W is exact.
+ *  - findNearestPeak (:596-630) does not use the detector: a strict > scan from maxMag = 0 over
+ *    int(f W / sr) +- peak_detection_width (an all-zero stretch leaves the target bin), then a strict local
+ *    maximum test at 1 .. K - 2.  Its magnitude is the smoothed one, its phase the unsmoothed spectrum's.
+ *    Several harmonics can return the same bin; it is then listed several times.
+ *  - The mask (:312-320) is laid around int(peak.Frequency W / sr), which can be one below BinIndex.
+ *  - noise_energy > 0 else 60 dB; harmonic_energy 0 with noise gives -Inf.
+ *  - HPS (:413-454): harmonics 2 .. min(5, max_harmonics); the scan starts from maxIdx 0, maxVal hps[0]
+ *    with a strict >, so when nothing beats bin 0 the f0 is 0 Hz and there are no harmonics.
+ *  - SPECTRAL (:463-512): the energies are sums over the peaks in [min_freq, max_freq], in the detector's
+ *    order; noise_energy = total_energy - harmonic_energy is exactly 0, and the ratio 60 dB, when every
+ *    peak is harmonic (two sums over the same terms in the same order).
+ * Errors: those of sonar_hratio_check; methods ACF and YIN (they need the samples), K != W / 2, F < 0, NULL
+ * mag with frames due -> SONAR_ERR_INVALID.  F == 0 succeeds and writes nothing. */
+int sonar_hratio_from_spectrum(sonar_ctx* ctx, const double* mag /* F x K */, const double* phase /* F x K or NULL */,
+                               int64_t F, int32_t K, const sonar_hratio_params* params, double* harmonic_ratio,
+                               double* harmonic_energy, double* noise_energy, double* total_energy, double* f0,
+                               double* f0_confidence, double* snr, double* periodicity, double* harmonicity,
+                               double* voicing, double* roughness, int32_t* num_harmonics,
+                               int32_t* h_bin /* F x max_harmonics */, double* h_freq, double* h_amp, double* h_phase,
+                               double* noise_floor /* F x K */, int32_t device_ptrs);
+
+/* AnalyzeFrame up to postProcessResult for every method, on the F = sonar_pitch_detect_frames(n, W, H)
+ * whole frames of pcm; the outputs are sonar_hratio_from_spectrum's.
+ *  - preprocessFrame (:260-270) multiplies by a Hann window with denominator W - 1 (:1004-1013).
+ *  - HNR, COMB, HPS, SPECTRAL: the W-point transform, |X| and atan2 of the first W / 2 bins, then the
+ *    stage above, one block per frame, nothing but results in device memory.  The transform is go-dsp's in
+ *    the reference: parity at tolerance.
+ *  - ACF (:385-411): AutoCorrelation.Compute of the windowed frame, the bits of sonar_autocorr on that
+ *    frame.  Correlations[0] is lag -(W - 1), not lag 0, so calculatePeriodicityFromACF's "excluding lag
+ *    0" (:823) excludes the wrong entry: periodicity and voicing are both max |corr| with lag 0 in it.
+ *    harmonic_ratio = 20 log10(max / (1 - max + 1e-10)): at W > 1000 (the un-normalised frequency-domain
+ *    regime, lag 0 of the order of W) the logarithm's argument is negative and the ratio is NaN; at
+ *    W <= 512 (Pearson, lag 0 = 1) it is 20 log10(1e10) = 200.  Every other output is 0.
+ *  - YIN (:515-542): a temporary PitchDetector with only method, rate, window and range set, on the
+ *    already windowed frame: its threshold is 0, pre-emphasis off, and the empty window name means Hann,
+ *    so the frame is windowed twice, (x w) w; min_confidence is 0 and there is no history.  Sets
+ *    harmonic_ratio = 20 log10(confidence + 1e-10), f0, f0_confidence, periodicity and voicing.  The
+ *    bits of sonar_pitch_frames_raw on the windowed frames.
+ * Errors: those of sonar_hratio_check; n < 0 or NULL pcm with frames due -> SONAR_ERR_INVALID. */
+int sonar_hratio_frames(sonar_ctx* ctx, const double* pcm, int64_t n, const sonar_hratio_params* params,
+                        double* harmonic_ratio, double* harmonic_energy, double* noise_energy, double* total_energy,
+                        double* f0, double* f0_confidence, double* snr, double* periodicity, double* harmonicity,
+                        double* voicing, double* roughness, int32_t* num_harmonics, int32_t* h_bin, double* h_freq,
+                        double* h_amp, double* h_phase, double* noise_floor, int32_t device_ptrs);
+
+/* postProcessResult + updateTemporalTracking (:926-1002) over F raw rows in order, from an empty history (a
+ * fresh analyzer, or one after Reset).  Host-only, no context.  Per frame: from the second frame on (and
+ * with use_temporal_smoothing) harmonic_ratio = 0.3 raw + 0.7 previous, previous being the last smoothed
+ * value; temporal_stability = max(0, 1 - sqrt(gonum variance) / mean) of the history once it has three
+ * entries and a mean > 0, else 0 (gonum's stat.Mean and stat.Variance restated, parity unpinned);
+ * temporal_coherence = exp(-mean |difference of neighbours| / 10) once it has two, else 0.  Both are
+ * computed BEFORE the frame's own value enters the history, which holds the last 2 temporal_smoothing_len
+ * smoothed values (none at 0: stability and coherence stay 0, the smoothing stops too).  raw_f0 is
+ * accepted for f0History, which nothing reads; it may be NULL, and so may every output. */
+int sonar_hratio_track(const sonar_hratio_params* params, int64_t F, const double* raw_harmonic_ratio,
+                       const double* raw_f0, double* harmonic_ratio, double* temporal_stability,
+                       double* temporal_coherence);
+
+/* AnalyzeSequence (:1042-1054) over the whole frames of pcm: sonar_hratio_frames, then sonar_hratio_track,
+ * in one call.  harmonic_ratio is the smoothed one; *frames receives F.  With device_ptrs, pcm and every
+ * output array are device pointers. */
+int sonar_hratio(sonar_ctx* ctx, const double* pcm, int64_t n, const sonar_hratio_params* params,
+                 double* harmonic_ratio, double* temporal_stability, double* temporal_coherence,
+                 double* harmonic_energy, double* noise_energy, double* total_energy, double* f0,
+                 double* f0_confidence, double* snr, double* periodicity, double* harmonicity, double* voicing,
+                 double* roughness, int32_t* num_harmonics, int32_t* h_bin, double* h_freq, double* h_amp,
+                 double* h_phase, double* noise_floor, int64_t* frames, int32_t device_ptrs);
+
+/* GetAverageHarmonicRatio (:1057-1077): the mean of the ratios above -60 (a NaN is not), 0 without any. */
+double sonar_hratio_average(const double* harmonic_ratio, int64_t n);
+/* ClassifyHarmonicRatio (:1130-1142) as SONAR_HRATIO_VERY_LOW .. VERY_HIGH (a NaN is "Very Low", the else
+ * branch), and Go's strings; NULL for a category outside the enum. */
+int32_t sonar_hratio_classify(double harmonic_ratio);
+const char* sonar_hratio_category_name(int32_t category);
+/* EstimateVoicingQuality (:1145-1148): 1 / (1 + exp(-0.1 (ratio - 5))). */
+double sonar_hratio_voicing_quality(double harmonic_ratio);
+
 /* result accessors: rows*cols float64 values, row-major; scalars are 1x1 */
 int sonar_result_get(const sonar_result* res, const char* name, const double** data, int64_t* rows,
                      int64_t* cols);

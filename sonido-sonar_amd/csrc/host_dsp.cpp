@@ -867,5 +867,31 @@ bool pitch_stability(const double* pitch, int64_t n, int sample_rate, int hop_si
   return true;
 }
 
+HratioRow HratioTracker::step(bool smoothing, int len, double raw) {
+  HratioRow r;
+  r.ratio = raw;
+  if (smoothing && !hist.empty()) r.ratio = 0.3 * raw + (1.0 - 0.3) * prev;    // applyTemporalSmoothing :939-947
+  const size_t n = hist.size();
+  if (n >= 3) {                                                                // calculateTemporalStability :949-964
+    double s = 0.0;
+    for (double v : hist) s += v;
+    const double mean = s / (double)n;
+    if (mean > 0) {
+      const double q = 1.0 - std::sqrt(gonum_variance(hist.data(), n)) / mean;
+      r.stability = q != q ? q : std::max(0.0, q);                             // math.Max: a NaN stays
+    }
+  }
+  if (n >= 2) {                                                                // calculateTemporalCoherence :966-986
+    double total = 0.0;
+    for (size_t i = 1; i < n; ++i) total += std::fabs(hist[i] - hist[i - 1]);
+    r.coherence = std::exp(-(total / (double)(n - 1)) / 10.0);
+  }
+  hist.push_back(r.ratio);                                                     // updateTemporalTracking :988-1002
+  const size_t keep = (size_t)std::max(len, 0) * 2;
+  if (hist.size() > keep) hist.erase(hist.begin(), hist.end() - (std::ptrdiff_t)keep);
+  prev = r.ratio;
+  return r;
+}
+
 }  // namespace host
 }  // namespace sonar

@@ -184,5 +184,18 @@ struct PitchTracker {
 // the empty map of fewer than two entries or fewer than two voiced ones
 bool pitch_stability(const double* pitch, int64_t n, int sample_rate, int hop_size, double out7[7]);
 
+
+// HarmonicRatioAnalyzer's postProcessResult + updateTemporalTracking (harmonic_ratio.go:926-1002).  One step
+// per raw frame, in order; a fresh tracker is a fresh analyzer (or one after Reset).  The stability is
+// 1 - sqrt(gonum_variance) / mean of the history (stat.Mean's sum sequential), the coherence
+// exp(-mean |difference| / 10); both before the frame's own smoothed ratio enters the history, which keeps
+// its last 2 len values.  len >= 0 (Go panics at :996 otherwise; the caller refuses it).
+struct HratioRow { double ratio = 0, stability = 0, coherence = 0; };
+struct HratioTracker {
+  std::vector<double> hist;        // hrHistory, oldest first
+  double prev = 0.0;               // previousHR
+  HratioRow step(bool smoothing, int len, double raw);
+};
+
 }  // namespace host
 }  // namespace sonar

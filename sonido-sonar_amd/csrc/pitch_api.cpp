@@ -18,9 +18,49 @@
 #include "staging.h"
 
 using sonar::detail::fail;
+using sonar::detail::pitch_twiddles;
+using sonar::detail::pitch_window;
 using sonar::detail::Staging;
 using sonar::detail::timed_begin;
 using sonar::detail::timed_end;
+
+// createWindowFunction (:317-345), cached per (type, W)
+const double* sonar::detail::pitch_window(sonar_ctx* c, int type, int W) {
+  const unsigned char* t = nullptr;
+  const int rc = sonar::detail::cached_table(c, "pitch.win." + std::to_string(type) + "." + std::to_string(W), "pitch window",
+      [&](std::vector<unsigned char>& img, int64_t&) {
+        img.resize((size_t)W * sizeof(double));
+        double* w = (double*)img.data();
+        const double d = (double)(W - 1);
+        for (int i = 0; i < W; ++i) {
+          const double x = (double)i;
+          switch (type) {
+            case SONAR_PITCH_WIN_HAMMING: w[i] = 0.54 - 0.46 * std::cos(2.0 * M_PI * x / d); break;
+            case SONAR_PITCH_WIN_BLACKMAN:
+              w[i] = 0.42 - 0.5 * std::cos(2.0 * M_PI * x / d) + 0.08 * std::cos(4.0 * M_PI * x / d);
+              break;
+            case SONAR_PITCH_WIN_RECTANGULAR: w[i] = 1.0; break;
+            default: w[i] = 0.5 * (1.0 - std::cos(2.0 * M_PI * x / d)); break;
+          }
+        }
+        return SONAR_OK;
+      }, &t);
+  return rc == SONAR_OK ? (const double*)t : nullptr;
+}
+
+// the N / 2 (cos, sin) pairs of -2 pi m / N: the table of sonar_xcorr_params' transform, under its key
+const double2* sonar::detail::pitch_twiddles(sonar_ctx* c, int64_t N) {
+  const unsigned char* tw = nullptr;
+  const int rc = sonar::detail::cached_table(c, "xcorr.tw." + std::to_string(N), "correlation FFT",
+      [&](std::vector<unsigned char>& img, int64_t&) {
+        const int64_t half = N / 2;
+        img.resize((size_t)half * sizeof(double2));
+        double2* h = (double2*)img.data();
+        for (int64_t m = 0; m < half; ++m) ::sincos(-2.0 * M_PI * (double)m / (double)N, &h[m].y, &h[m].x);
+        return SONAR_OK;
+      }, &tw);
+  return rc == SONAR_OK ? (const double2*)tw : nullptr;
+}
 
 namespace {
 
@@ -110,44 +150,6 @@ int check_params(const sonar_pitch_params* p, Plan* pl, std::string& msg) {
     default: pl->width = 0; break;
   }
   return SONAR_OK;
-}
-
-// createWindowFunction (:317-345), cached per (type, W)
-const double* pitch_window(sonar_ctx* c, int type, int W) {
-  const unsigned char* t = nullptr;
-  const int rc = sonar::detail::cached_table(c, "pitch.win." + std::to_string(type) + "." + std::to_string(W), "pitch window",
-      [&](std::vector<unsigned char>& img, int64_t&) {
-        img.resize((size_t)W * sizeof(double));
-        double* w = (double*)img.data();
-        const double d = (double)(W - 1);
-        for (int i = 0; i < W; ++i) {
-          const double x = (double)i;
-          switch (type) {
-            case SONAR_PITCH_WIN_HAMMING: w[i] = 0.54 - 0.46 * std::cos(2.0 * M_PI * x / d); break;
-            case SONAR_PITCH_WIN_BLACKMAN:
-              w[i] = 0.42 - 0.5 * std::cos(2.0 * M_PI * x / d) + 0.08 * std::cos(4.0 * M_PI * x / d);
-              break;
-            case SONAR_PITCH_WIN_RECTANGULAR: w[i] = 1.0; break;
-            default: w[i] = 0.5 * (1.0 - std::cos(2.0 * M_PI * x / d)); break;
-          }
-        }
-        return SONAR_OK;
-      }, &t);
-  return rc == SONAR_OK ? (const double*)t : nullptr;
-}
-
-// the N / 2 (cos, sin) pairs of -2 pi m / N: the table of sonar_xcorr_params' transform, under its key
-const double2* pitch_twiddles(sonar_ctx* c, int64_t N) {
-  const unsigned char* tw = nullptr;
-  const int rc = sonar::detail::cached_table(c, "xcorr.tw." + std::to_string(N), "correlation FFT",
-      [&](std::vector<unsigned char>& img, int64_t&) {
-        const int64_t half = N / 2;
-        img.resize((size_t)half * sizeof(double2));
-        double2* h = (double2*)img.data();
-        for (int64_t m = 0; m < half; ++m) ::sincos(-2.0 * M_PI * (double)m / (double)N, &h[m].y, &h[m].x);
-        return SONAR_OK;
-      }, &tw);
-  return rc == SONAR_OK ? (const double2*)tw : nullptr;
 }
 
 struct RawOut {

@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+struct sonar_ctx;
+
 namespace sonar {
 
 constexpr int PITCH_MIN_W = 64, PITCH_MAX_W = 2048;   // powers of two; W * zero_padding and the ACF's 2 W
@@ -33,5 +35,13 @@ struct PitchArgs {
 
 // 0, -1 for a shape the kernels do not take, -5 for a launch error
 int launch_pitch_frames(const PitchArgs& a, hipStream_t s);
+
+namespace detail {
+// The cached device tables of the pitch entries (pitch_api.cpp), which the harmonic-ratio entries share:
+// createWindowFunction's window (SONAR_PITCH_WIN_*, denominator W - 1) and the N / 2 (cos, sin) pairs of
+// -2 pi m / N.  Null after a failure, whose code and text the context holds.
+const double* pitch_window(sonar_ctx* c, int type, int W);
+const double2* pitch_twiddles(sonar_ctx* c, int64_t N);
+}  // namespace detail
 
 }  // namespace sonar

@@ -16,6 +16,9 @@ package sonargpu
 // DetectPitch's switch through sonar_pitch_frames_raw, sonar_pitch_track, sonar_pitch_detect and
 // sonar_pitch_stability.
 //
+// HarmonicRatioAnalyzer seam (algorithms/tonal/harmonic_ratio.go), at the end of this file: AnalyzeSequence
+// over one signal through sonar_hratio, and the helpers through their host-only entries.
+//
 // Written against include/sonar_gpu.h; not compiled here (no Go toolchain in the image).
 
 /*
@@ -1316,4 +1319,212 @@ func GetPitchDetectionMethodName(method PitchDetectionMethod) string {
 		return names[method]
 	}
 	return "Unknown"
+}
+
+// ---- HarmonicRatioAnalyzer seam (algorithms/tonal/harmonic_ratio.go): NewHarmonicRatioAnalyzer,
+// NewHarmonicRatioAnalyzerWithParams, AnalyzeSequence over the whole frames of one signal,
+// GetAverageHarmonicRatio, ClassifyHarmonicRatio and EstimateVoicingQuality through sonar_hratio and its
+// host-only companions.  The library returns arrays; this file rebuilds HarmonicRatioResult.
+
+// HarmonicRatioMethod carries the reference's values (:17-24), which are SONAR_HRATIO_*.
+type HarmonicRatioMethod int
+
+const (
+	HarmonicRatioHNR HarmonicRatioMethod = iota
+	HarmonicRatioACF
+	HarmonicRatioHPS
+	HarmonicRatioComb
+	HarmonicRatioSpectral
+	HarmonicRatioYin
+)
+
+// HarmonicRatioParams = tonal.HarmonicRatioParams (:27-57).  AutocorrMaxLag is the argument of the
+// analyzer's NewAutoCorrelation: 2048 from NewHarmonicRatioAnalyzer, WindowSize from ...WithParams.
+type HarmonicRatioParams struct {
+	Method                                                       HarmonicRatioMethod
+	SampleRate, WindowSize, HopSize                              int
+	MinFreq, MaxFreq                                             float64
+	MaxHarmonics                                                 int
+	HarmonicTolerance, MinPeakHeight                             float64
+	PeakDetectionWidth, SpectralSmoothingLen                     int
+	NoiseFloorMethod                                             string
+	NoiseFloorPercentile                                         float64
+	NoiseFloorSmoothingLen                                       int
+	UseTemporalSmoothing                                         bool
+	TemporalSmoothingLen                                         int
+	UseFreqWeighting, UsePsychoacousticMask, AdaptiveThreshold   bool
+	AutocorrMaxLag                                               int
+}
+
+// HarmonicPeak holds the fields of harmonic.SpectralPeak that findNearestPeak fills.
+type HarmonicPeak struct {
+	Frequency, Magnitude, Phase float64
+	BinIndex, Harmonic          int
+}
+
+// HarmonicRatioResult = tonal.HarmonicRatioResult (:60-98); ProcessingTime is 0 as in the reference
+// (getCurrentTime is a placeholder).  HarmonicFrequencies, Amplitudes and Phases are set by the HNR and
+// Comb methods only, as in the reference; SpectralPeaks by the four spectral methods.
+type HarmonicRatioResult struct {
+	HarmonicRatio, HarmonicEnergy, NoiseEnergy, TotalEnergy            float64
+	HarmonicFrequencies, HarmonicAmplitudes, HarmonicPhases            []float64
+	F0Frequency, F0Confidence, F0Strength                              float64
+	SpectralPeaks                                                      []HarmonicPeak
+	NoiseFloor                                                         []float64
+	SignalToNoiseRatio, Periodicity, Harmonicity, Voicing, Roughness   float64
+	TemporalStability, TemporalCoherence                               float64
+	Method                                                             string
+	ProcessingTime                                                     float64
+	NumHarmonics                                                       int
+	AnalysisFreqRange                                                  [2]float64
+}
+
+// HarmonicRatioAnalyzer holds the parameters; the device work is per call.
+type HarmonicRatioAnalyzer struct {
+	x      *Context
+	params HarmonicRatioParams
+}
+
+// NewHarmonicRatioAnalyzer = tonal.NewHarmonicRatioAnalyzer (:130-161), through sonar_hratio_params_default.
+func (x *Context) NewHarmonicRatioAnalyzer(sampleRate int) *HarmonicRatioAnalyzer {
+	var p C.sonar_hratio_params
+	C.sonar_hratio_params_default(&p, C.int32_t(sampleRate))
+	return &HarmonicRatioAnalyzer{x: x, params: HarmonicRatioParams{
+		Method: HarmonicRatioMethod(p.method), SampleRate: int(p.sample_rate), WindowSize: int(p.window_size),
+		HopSize: int(p.hop_size), MinFreq: float64(p.min_freq), MaxFreq: float64(p.max_freq),
+		MaxHarmonics: int(p.max_harmonics), HarmonicTolerance: float64(p.harmonic_tolerance),
+		MinPeakHeight: float64(p.min_peak_height), PeakDetectionWidth: int(p.peak_detection_width),
+		SpectralSmoothingLen: int(p.spectral_smoothing_len), NoiseFloorMethod: "percentile",
+		NoiseFloorPercentile: float64(p.noise_floor_percentile), NoiseFloorSmoothingLen: int(p.noise_floor_smoothing_len),
+		UseTemporalSmoothing: p.use_temporal_smoothing != 0, TemporalSmoothingLen: int(p.temporal_smoothing_len),
+		AutocorrMaxLag: int(p.autocorr_max_lag)}}
+}
+
+// NewHarmonicRatioAnalyzerWithParams = tonal.NewHarmonicRatioAnalyzerWithParams (:164-178): its
+// autocorrelation is NewAutoCorrelation(WindowSize), which an AutocorrMaxLag of 0 selects.
+func (x *Context) NewHarmonicRatioAnalyzerWithParams(params HarmonicRatioParams) *HarmonicRatioAnalyzer {
+	if params.AutocorrMaxLag == 0 {
+		params.AutocorrMaxLag = params.WindowSize
+	}
+	return &HarmonicRatioAnalyzer{x: x, params: params}
+}
+
+func (hra *HarmonicRatioAnalyzer) cParams() C.sonar_hratio_params {
+	p := hra.params
+	nf := C.int32_t(C.SONAR_HRATIO_NOISE_PERCENTILE) // estimateNoiseFloor: every unknown string is "percentile" (:640)
+	switch p.NoiseFloorMethod {
+	case "median":
+		nf = C.SONAR_HRATIO_NOISE_MEDIAN
+	case "minimum":
+		nf = C.SONAR_HRATIO_NOISE_MINIMUM
+	}
+	return C.sonar_hratio_params{method: C.int32_t(p.Method), sample_rate: C.int32_t(p.SampleRate),
+		window_size: C.int32_t(p.WindowSize), hop_size: C.int32_t(p.HopSize), min_freq: C.double(p.MinFreq),
+		max_freq: C.double(p.MaxFreq), max_harmonics: C.int32_t(p.MaxHarmonics),
+		harmonic_tolerance: C.double(p.HarmonicTolerance), min_peak_height: C.double(p.MinPeakHeight),
+		peak_detection_width: C.int32_t(p.PeakDetectionWidth), spectral_smoothing_len: C.int32_t(p.SpectralSmoothingLen),
+		noise_floor_method: nf, noise_floor_percentile: C.double(p.NoiseFloorPercentile),
+		noise_floor_smoothing_len: C.int32_t(p.NoiseFloorSmoothingLen), use_temporal_smoothing: b2i(p.UseTemporalSmoothing),
+		temporal_smoothing_len: C.int32_t(p.TemporalSmoothingLen), use_freq_weighting: b2i(p.UseFreqWeighting),
+		use_psychoacoustic_mask: b2i(p.UsePsychoacousticMask), adaptive_threshold: b2i(p.AdaptiveThreshold),
+		autocorr_max_lag: C.int32_t(p.AutocorrMaxLag)}
+}
+
+// GetHarmonicRatioMethodName = getMethodName (:1015-1032).
+func GetHarmonicRatioMethodName(method HarmonicRatioMethod) string {
+	names := GetSupportedHarmonicRatioMethods()
+	if method >= 0 && int(method) < len(names) {
+		return names[method]
+	}
+	return "Unknown"
+}
+
+// GetSupportedHarmonicRatioMethods = tonal.GetSupportedHarmonicRatioMethods (:1118-1127).
+func GetSupportedHarmonicRatioMethods() []string {
+	return []string{"Harmonic-to-Noise Ratio", "Autocorrelation Function", "Harmonic Product Spectrum", "Comb Filtering",
+		"Spectral Peak Analysis", "YIN-based"}
+}
+
+// AnalyzeSignal is AnalyzeSequence (:1042-1054) over the whole frames of one signal (WindowSize samples
+// every HopSize) on a fresh history, in one sonar_hratio call.
+func (hra *HarmonicRatioAnalyzer) AnalyzeSignal(pcm []float64) ([]HarmonicRatioResult, error) {
+	p := hra.cParams()
+	F := int(C.sonar_pitch_detect_frames(C.int64_t(len(pcm)), p.window_size, p.hop_size))
+	if F == 0 {
+		if rc := C.sonar_hratio_check(&p); rc != C.SONAR_OK {
+			return nil, fmt.Errorf("harmonic ratio: parameters refused (%d)", int(rc))
+		}
+		return []HarmonicRatioResult{}, nil
+	}
+	mh := hra.params.MaxHarmonics
+	if mh < 0 {
+		mh = 0
+	}
+	K := hra.params.WindowSize / 2
+	cols := make([][]float64, 13)
+	for k := range cols {
+		cols[k] = make([]float64, F)
+	}
+	num, hbin := make([]int32, F), make([]int32, F*mh+1)
+	hf, ha, hp := make([]float64, F*mh+1), make([]float64, F*mh+1), make([]float64, F*mh+1)
+	floor := make([]float64, F*K)
+	var frames C.int64_t
+	if rc := C.sonar_hratio(hra.x.c, f64p(pcm), C.int64_t(len(pcm)), &p, f64p(cols[0]), f64p(cols[1]), f64p(cols[2]),
+		f64p(cols[3]), f64p(cols[4]), f64p(cols[5]), f64p(cols[6]), f64p(cols[7]), f64p(cols[8]), f64p(cols[9]),
+		f64p(cols[10]), f64p(cols[11]), f64p(cols[12]), i32p(num), i32p(hbin), f64p(hf), f64p(ha), f64p(hp), f64p(floor),
+		&frames, 0); rc != C.SONAR_OK {
+		return nil, hra.x.err(rc)
+	}
+	m := hra.params.Method
+	hnr := m != HarmonicRatioACF && m != HarmonicRatioHPS && m != HarmonicRatioSpectral && m != HarmonicRatioYin
+	out := make([]HarmonicRatioResult, F)
+	for t := range out {
+		r := &out[t]
+		r.HarmonicRatio, r.TemporalStability, r.TemporalCoherence = cols[0][t], cols[1][t], cols[2][t]
+		r.HarmonicEnergy, r.NoiseEnergy, r.TotalEnergy = cols[3][t], cols[4][t], cols[5][t]
+		r.F0Frequency, r.F0Confidence, r.SignalToNoiseRatio = cols[6][t], cols[7][t], cols[8][t]
+		r.Periodicity, r.Harmonicity, r.Voicing, r.Roughness = cols[9][t], cols[10][t], cols[11][t], cols[12][t]
+		r.NumHarmonics = int(num[t])
+		if m != HarmonicRatioACF && m != HarmonicRatioYin {
+			r.SpectralPeaks = make([]HarmonicPeak, num[t])
+			for s := range r.SpectralPeaks {
+				o := t*mh + s
+				// findHarmonicPeaks numbers the harmonic it looked for (:587); the library keeps the order, not the
+				// number, so Harmonic is the nearest multiple of f0: the one looked for whenever the peak lies within
+				// half an f0 of its target
+				r.SpectralPeaks[s] = HarmonicPeak{Frequency: hf[o], Magnitude: ha[o], Phase: hp[o], BinIndex: int(hbin[o]),
+					Harmonic: int(math.Round(hf[o]/r.F0Frequency)) - 1}
+			}
+		}
+		if hnr {
+			r.F0Strength = r.F0Confidence
+			r.NoiseFloor = floor[t*K : (t+1)*K : (t+1)*K]
+			r.HarmonicFrequencies, r.HarmonicAmplitudes, r.HarmonicPhases = hf[t*mh:t*mh+int(num[t])], ha[t*mh:t*mh+int(num[t])], hp[t*mh:t*mh+int(num[t])]
+		}
+		r.Method = GetHarmonicRatioMethodName(m)
+		r.AnalysisFreqRange = [2]float64{hra.params.MinFreq, hra.params.MaxFreq}
+	}
+	return out, nil
+}
+
+func (hra *HarmonicRatioAnalyzer) GetParameters() HarmonicRatioParams       { return hra.params }
+func (hra *HarmonicRatioAnalyzer) SetParameters(params HarmonicRatioParams) { hra.params = params }
+
+// GetAverageHarmonicRatio = HarmonicRatioAnalyzer.GetAverageHarmonicRatio (:1057-1077).
+func (hra *HarmonicRatioAnalyzer) GetAverageHarmonicRatio(results []HarmonicRatioResult) float64 {
+	r := make([]float64, len(results))
+	for i := range results {
+		r[i] = results[i].HarmonicRatio
+	}
+	return float64(C.sonar_hratio_average(f64p(r), C.int64_t(len(r))))
+}
+
+// ClassifyHarmonicRatio = tonal.ClassifyHarmonicRatio (:1130-1142).
+func ClassifyHarmonicRatio(harmonicRatio float64) string {
+	return C.GoString(C.sonar_hratio_category_name(C.sonar_hratio_classify(C.double(harmonicRatio))))
+}
+
+// EstimateVoicingQuality = tonal.EstimateVoicingQuality (:1145-1148).
+func EstimateVoicingQuality(harmonicRatio float64) float64 {
+	return float64(C.sonar_hratio_voicing_quality(C.double(harmonicRatio)))
 }

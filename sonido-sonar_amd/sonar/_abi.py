@@ -381,6 +381,22 @@ def lib():
     L.sonar_pitch_track.argtypes = [C.POINTER(PitchParams), C.c_int64] + [_vp] * 13
     L.sonar_pitch_detect.argtypes = [_vp, _vp, C.c_int64, C.POINTER(PitchParams)] + [_vp] * 9 + [_i64p, C.c_int32]
     L.sonar_pitch_stability.argtypes = [_vp, C.c_int64, C.c_int32, C.c_int32, _vp, _i32p]
+    L.sonar_hratio_params_default.argtypes = [C.POINTER(HratioParams), C.c_int32]
+    L.sonar_hratio_params_default.restype = None
+    L.sonar_hratio_check.argtypes = [C.POINTER(HratioParams)]
+    L.sonar_hratio_from_spectrum.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int32, C.POINTER(HratioParams)] + [_vp] * 17 + \
+        [C.c_int32]
+    L.sonar_hratio_frames.argtypes = [_vp, _vp, C.c_int64, C.POINTER(HratioParams)] + [_vp] * 17 + [C.c_int32]
+    L.sonar_hratio_track.argtypes = [C.POINTER(HratioParams), C.c_int64] + [_vp] * 5
+    L.sonar_hratio.argtypes = [_vp, _vp, C.c_int64, C.POINTER(HratioParams)] + [_vp] * 19 + [_i64p, C.c_int32]
+    L.sonar_hratio_average.argtypes = [_vp, C.c_int64]
+    L.sonar_hratio_average.restype = C.c_double
+    L.sonar_hratio_classify.argtypes = [C.c_double]
+    L.sonar_hratio_classify.restype = C.c_int32
+    L.sonar_hratio_category_name.argtypes = [C.c_int32]
+    L.sonar_hratio_category_name.restype = C.c_char_p
+    L.sonar_hratio_voicing_quality.argtypes = [C.c_double]
+    L.sonar_hratio_voicing_quality.restype = C.c_double
     L.sonar_music_alignment_features.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_dtw.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, _d, _vp, _vp, _vp, _i64p,
@@ -860,6 +876,102 @@ def pitch_stability(pitch, sample_rate, hop_size=512):
     return {} if empty.value else dict(zip(PITCH_STABILITY_KEYS, out.tolist()))
 
 
+# HarmonicRatioMethod (SONAR_HRATIO_*, harmonic_ratio.go:17-24), NoiseFloorMethod's strings
+# (SONAR_HRATIO_NOISE_*), getMethodName's names by code and the per-frame outputs in the entries' order
+HRATIO_METHODS = {"hnr": 0, "acf": 1, "hps": 2, "comb": 3, "spectral": 4, "yin": 5}
+HRATIO_NOISE_METHODS = {"median": 0, "percentile": 1, "minimum": 2}
+HRATIO_METHOD_NAMES = ["Harmonic-to-Noise Ratio", "Autocorrelation Function", "Harmonic Product Spectrum",
+                       "Comb Filtering", "Spectral Peak Analysis", "YIN-based"]
+HRATIO_CATEGORIES = ["Very Low", "Low", "Medium", "High", "Very High"]
+HRATIO_FRAME_FIELDS = ("harmonic_ratio", "harmonic_energy", "noise_energy", "total_energy", "f0", "f0_confidence", "snr",
+                       "periodicity", "harmonicity", "voicing", "roughness", "num_harmonics", "h_bin", "h_freq", "h_amp",
+                       "h_phase", "noise_floor")
+HRATIO_FIELDS = ("harmonic_ratio", "temporal_stability", "temporal_coherence") + HRATIO_FRAME_FIELDS[1:]
+HRATIO_MAX_HARMONICS = 64
+
+
+class HratioParams(C.Structure):
+    """sonar_hratio_params (HarmonicRatioParams, harmonic_ratio.go:27-57, field for field, and
+    autocorr_max_lag)."""
+    _fields_ = [(n, C.c_int32) for n in ("method", "sample_rate", "window_size", "hop_size")] + \
+               [("min_freq", C.c_double), ("max_freq", C.c_double), ("max_harmonics", C.c_int32),
+                ("harmonic_tolerance", C.c_double), ("min_peak_height", C.c_double),
+                ("peak_detection_width", C.c_int32), ("spectral_smoothing_len", C.c_int32),
+                ("noise_floor_method", C.c_int32), ("noise_floor_percentile", C.c_double)] + \
+               [(n, C.c_int32) for n in ("noise_floor_smoothing_len", "use_temporal_smoothing", "temporal_smoothing_len",
+                                         "use_freq_weighting", "use_psychoacoustic_mask", "adaptive_threshold",
+                                         "autocorr_max_lag")]
+
+
+def hratio_params_default(sample_rate, **kw):
+    """sonar_hratio_params_default: NewHarmonicRatioAnalyzer(sample_rate)'s parameters, then the overrides.
+    method and noise_floor_method take their names; a noise floor name Go does not know is "percentile",
+    as in estimateNoiseFloor."""
+    p = HratioParams()
+    lib().sonar_hratio_params_default(C.byref(p), int(sample_rate))
+    for k, v in kw.items():
+        if k == "method" and isinstance(v, str):
+            v = HRATIO_METHODS[v]
+        if k == "noise_floor_method" and isinstance(v, str):
+            v = HRATIO_NOISE_METHODS.get(v, 1)
+        if not hasattr(p, k):
+            raise TypeError(f"unknown harmonic ratio parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def hratio_method_name(method):
+    """getMethodName (:1015-1032)."""
+    return HRATIO_METHOD_NAMES[method] if 0 <= method < len(HRATIO_METHOD_NAMES) else "Unknown"
+
+
+def hratio_check(params):
+    """sonar_hratio_check (host only): SONAR_OK or the code of a parameter set the entries refuse."""
+    return int(lib().sonar_hratio_check(C.byref(params)))
+
+
+def hratio_track(params, raw_harmonic_ratio, raw_f0=None):
+    """sonar_hratio_track (host only): postProcessResult + updateTemporalTracking over raw rows in order,
+    from an empty history -> dict of harmonic_ratio, temporal_stability, temporal_coherence."""
+    r = _f64(raw_harmonic_ratio)
+    f0 = None if raw_f0 is None else _f64(raw_f0)
+    F = len(r)
+    out = {k: np.zeros(F) for k in HRATIO_FIELDS[:3]}
+    rc = lib().sonar_hratio_track(C.byref(params), F, _ptr(r), _ptr(f0), *[_ptr(out[k]) for k in HRATIO_FIELDS[:3]])
+    if rc != OK:
+        raise SonarError(rc, "runtime error: slice bounds out of range [%d:1]" % (1 - 2 * params.temporal_smoothing_len)
+                         if rc == ERR_PANIC else "sonar_hratio_track")
+    return out
+
+
+def hratio_average(harmonic_ratio):
+    """sonar_hratio_average (host only): GetAverageHarmonicRatio."""
+    r = _f64(harmonic_ratio)
+    return float(lib().sonar_hratio_average(_ptr(r) if len(r) else None, len(r)))
+
+
+def hratio_classify(harmonic_ratio):
+    """sonar_hratio_classify (host only): ClassifyHarmonicRatio's string."""
+    L = lib()
+    return L.sonar_hratio_category_name(L.sonar_hratio_classify(float(harmonic_ratio))).decode()
+
+
+def hratio_voicing_quality(harmonic_ratio):
+    """sonar_hratio_voicing_quality (host only): EstimateVoicingQuality."""
+    return float(lib().sonar_hratio_voicing_quality(float(harmonic_ratio)))
+
+
+def _hratio_arrays(F, K, mh, want):
+    """host arrays of the wanted per-frame outputs (None for the others), in HRATIO_FRAME_FIELDS' order"""
+    shape = {"num_harmonics": ((F,), np.int32), "h_bin": ((F, mh), np.int32), "h_freq": ((F, mh), np.float64),
+             "h_amp": ((F, mh), np.float64), "h_phase": ((F, mh), np.float64), "noise_floor": ((F, K), np.float64)}
+    out = {}
+    for k in HRATIO_FRAME_FIELDS:
+        s, t = shape.get(k, ((F,), np.float64))
+        out[k] = np.zeros(s, t) if (want is None or k in want) else None
+    return out
+
+
 _ONSET_ERRORS = {ERR_UNSUPPORTED: "onsets: parameters the library does not reproduce (include/sonar_gpu.h)",
                  ERR_INVALID: "onsets: invalid argument"}
 
@@ -1226,6 +1338,59 @@ class Context:
         self._check(self._L.sonar_pitch_detect(self._h, pcm_ptr, int(n), C.byref(params),
                                                *[out_ptrs.get(k) for k in PITCH_TRACK_FIELDS], C.byref(frames), 1))
         return frames.value
+
+    def hratio_from_spectrum(self, mag, params, phase=None, want=None):
+        """Everything AnalyzeFrame does after the transform (HNR, Comb, HPS, Spectral) on rows of W / 2
+        unsmoothed magnitudes (sonar_hratio_from_spectrum) -> dict of HRATIO_FRAME_FIELDS; `want` names the
+        outputs to compute (all by default), the others are None."""
+        mag = np.atleast_2d(_f64(mag))
+        F, K = mag.shape
+        ph = None if phase is None else np.atleast_2d(_f64(phase))
+        out = _hratio_arrays(F, K, max(params.max_harmonics, 0), want)
+        self._check(self._L.sonar_hratio_from_spectrum(self._h, _ptr(mag) if F else None, _ptr(ph), F, K, C.byref(params),
+                                                       *[_ptr(out[k]) for k in HRATIO_FRAME_FIELDS], 0))
+        return out
+
+    def hratio_frames(self, pcm, params, want=None):
+        """AnalyzeFrame up to postProcessResult per whole frame of pcm, every method (sonar_hratio_frames) ->
+        dict of HRATIO_FRAME_FIELDS."""
+        pcm = _f64(pcm)
+        F = pitch_detect_frames(len(pcm), params.window_size, params.hop_size)
+        out = _hratio_arrays(F, max(params.window_size // 2, 0), max(params.max_harmonics, 0), want)
+        self._check(self._L.sonar_hratio_frames(self._h, _ptr(pcm) if len(pcm) else None, len(pcm), C.byref(params),
+                                                *[_ptr(out[k]) for k in HRATIO_FRAME_FIELDS], 0))
+        return out
+
+    def hratio(self, pcm, params, want=None):
+        """AnalyzeSequence over the whole frames of pcm (sonar_hratio): the per-frame pass, then the tracker
+        -> dict of HRATIO_FIELDS."""
+        pcm = _f64(pcm)
+        F = pitch_detect_frames(len(pcm), params.window_size, params.hop_size)
+        fr = _hratio_arrays(F, max(params.window_size // 2, 0), max(params.max_harmonics, 0), want)
+        out = {k: (np.zeros(F) if (want is None or k in want) else None) for k in HRATIO_FIELDS[:3]}
+        out.update({k: fr[k] for k in HRATIO_FRAME_FIELDS[1:]})
+        frames = C.c_int64()
+        self._check(self._L.sonar_hratio(self._h, _ptr(pcm) if len(pcm) else None, len(pcm), C.byref(params),
+                                         *[_ptr(out[k]) for k in HRATIO_FIELDS], C.byref(frames), 0))
+        assert frames.value == F
+        return out
+
+    def hratio_device(self, entry, pcm_ptr, n, params, out_ptrs):
+        """sonar_hratio_frames ("frames") or sonar_hratio ("sequence") on device memory (device_ptrs = 1):
+        out_ptrs maps output names to device addresses (missing: not wanted) -> the frame count."""
+        if entry == "frames":
+            self._check(self._L.sonar_hratio_frames(self._h, pcm_ptr, int(n), C.byref(params),
+                                                    *[out_ptrs.get(k) for k in HRATIO_FRAME_FIELDS], 1))
+            return pitch_detect_frames(int(n), params.window_size, params.hop_size)
+        frames = C.c_int64()
+        self._check(self._L.sonar_hratio(self._h, pcm_ptr, int(n), C.byref(params),
+                                         *[out_ptrs.get(k) for k in HRATIO_FIELDS], C.byref(frames), 1))
+        return frames.value
+
+    def hratio_from_spectrum_device(self, mag_ptr, phase_ptr, F, K, params, out_ptrs):
+        """hratio_from_spectrum on device memory (device_ptrs = 1)."""
+        self._check(self._L.sonar_hratio_from_spectrum(self._h, mag_ptr, phase_ptr, int(F), int(K), C.byref(params),
+                                                       *[out_ptrs.get(k) for k in HRATIO_FRAME_FIELDS], 1))
 
     def chroma_stft(self, pcm, n_frames, hop, sample_rate, preprocess=True):
         pcm = _f64(pcm)
