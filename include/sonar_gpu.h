@@ -1900,6 +1900,212 @@ const char* sonar_hratio_category_name(int32_t category);
 /* EstimateVoicingQuality (:1145-1148): 1 / (1 + exp(-0.1 (ratio - 5))). */
 double sonar_hratio_voicing_quality(double harmonic_ratio);
 
+/* ---- InharmonicityAnalyzer (algorithms/tonal/inharmonicity.go): AnalyzeFrame's harmonic search, every
+ * method of its switch (:252-267), the physical model, the quality metrics, the temporal
+ * tracking, AnalyzeSequence and the helpers.  Everything is float64.  sonar_extract_music_features keeps
+ * writing its inharmonicity_ratio row as zeros; these entries are the analyzer itself.
+ * DESIGN.md F100-F107 record the reference's quirks. --------------------------------------------------- */
+enum {                             /* InharmonicityMethod (:17-24), Go's values; every other value is
+                                      SpectralDeviation, the switch's default case (:265) */
+  SONAR_INHARM_RAILSBACK = 0,
+  SONAR_INHARM_FLETCHER_MUNSON = 1,
+  SONAR_INHARM_SPECTRAL_DEVIATION = 2,
+  SONAR_INHARM_PARTIAL_TRACKING = 3,   /* calculatePartialTrackingInharmonicity is SpectralDeviation (:548) */
+  SONAR_INHARM_BEAT_PATTERN = 4,       /* needs the samples: sonar_inharm_frames and sonar_inharm only */
+  SONAR_INHARM_STATISTICAL = 5
+};
+enum {                             /* InharmonicityModel (:29-34); only STRING changes a result (:847-896) */
+  SONAR_INHARM_MODEL_STRING = 0, SONAR_INHARM_MODEL_PIPE = 1, SONAR_INHARM_MODEL_MEMBRANE = 2,
+  SONAR_INHARM_MODEL_GENERAL = 3
+};
+enum {                             /* AnalysisQuality: assessAnalysisQuality's five strings (:1103-1137) and the
+                                      early return's (:240); -1 on an INSUFFICIENT row, which has no result */
+  SONAR_INHARM_QUALITY_VERY_POOR = 0, SONAR_INHARM_QUALITY_POOR = 1, SONAR_INHARM_QUALITY_FAIR = 2,
+  SONAR_INHARM_QUALITY_GOOD = 3, SONAR_INHARM_QUALITY_EXCELLENT = 4, SONAR_INHARM_QUALITY_INVALID_F0 = 5
+};
+enum {                             /* what AnalyzeFrame returned for the frame */
+  SONAR_INHARM_STATUS_OK = 0,
+  SONAR_INHARM_STATUS_INVALID_F0 = 1,    /* the nil-error early return of :236-242 */
+  SONAR_INHARM_STATUS_INSUFFICIENT = 2   /* the error of :369, "insufficient harmonics found: %d < %d" */
+};
+enum {                             /* ClassifyInharmonicity (:1272-1286) */
+  SONAR_INHARM_VERY_LOW = 0, SONAR_INHARM_LOW = 1, SONAR_INHARM_MODERATE = 2, SONAR_INHARM_HIGH = 3,
+  SONAR_INHARM_VERY_HIGH = 4
+};
+enum {                             /* EstimateInstrumentType (:1289-1313) */
+  SONAR_INHARM_INSTRUMENT_PIANO_STRING = 0, SONAR_INHARM_INSTRUMENT_WIND_BRASS = 1,
+  SONAR_INHARM_INSTRUMENT_PLUCKED_STRING = 2, SONAR_INHARM_INSTRUMENT_VOCAL_HARMONIC = 3,
+  SONAR_INHARM_INSTRUMENT_UNKNOWN = 4
+};
+#define SONAR_INHARM_MAX_HARMONICS 64
+/* InharmonicityParams (:37-72) field for field.  The reference never reads freq_resolution,
+ * reference_harmonic, use_log_frequency, string_stiffness and confidence_level; the library ignores them
+ * as well. */
+typedef struct sonar_inharm_params {
+  int32_t method;                  /* SONAR_INHARM_* */
+  int32_t model;                   /* SONAR_INHARM_MODEL_* */
+  int32_t sample_rate;
+  int32_t window_size;
+  int32_t max_harmonics;
+  int32_t min_harmonics;
+  double harmonic_tolerance;
+  double min_harmonic_strength;
+  double min_freq, max_freq;
+  double freq_resolution;          /* never read */
+  int32_t reference_harmonic;      /* never read */
+  int32_t weight_by_amplitude;     /* 0 / 1 */
+  int32_t use_log_frequency;       /* never read */
+  double string_tension, string_length;
+  double string_stiffness;         /* never read */
+  double outlier_threshold;
+  double confidence_level;         /* never read */
+  int32_t use_robust_estimation;   /* 0 / 1 */
+  int32_t use_temporal_tracking;   /* 0 / 1 */
+  int32_t temporal_window;
+} sonar_inharm_params;
+
+/* NewInharmonicityAnalyzer(sample_rate) (:147-172): SpectralDeviation, the General model, window 4096, 20 / 3
+ * harmonics, tolerance 0.05, strength 0.01, 80-2000 Hz, resolution 1, reference harmonic 1, amplitude weights
+ * on, log frequency off, tension 1, length 1, stiffness 0.001, outlier threshold 2, confidence level 0.95,
+ * robust estimation on, temporal tracking off over a window of 10.  The window of 4096 is the constructor's:
+ * the analyzer's own PitchDetector takes frames of 1024 only (F100), so AnalyzeFrame fails at every frame
+ * length with these defaults, and sonar_inharm_frames says so in Go's words. */
+void sonar_inharm_params_default(sonar_inharm_params* p, int32_t sample_rate);
+
+/* The parameter checks of the entries below, without a device.  SONAR_OK or a negative SONAR_ERR_*:
+ *   NULL params -> SONAR_ERR_INVALID;
+ *   sample_rate < 1 -> SONAR_ERR_INVALID;
+ *   min_freq, max_freq, harmonic_tolerance or min_harmonic_strength not finite -> SONAR_ERR_INVALID (a
+ *     documented narrowing: Go would convert an infinity or a NaN to int);
+ *   max_harmonics > 64, or a search window max_freq (1 + |harmonic_tolerance|) window_size / sample_rate
+ *     beyond 2^31 bins -> SONAR_ERR_UNSUPPORTED.
+ * A negative temporal_window with use_temporal_tracking is not refused here: it is SONAR_ERR_PANIC "runtime
+ * error: slice bounds out of range [a:1]", a = 1 + |temporal_window| (inharmonicityHistory[len - maxHistory:]
+ * :1098, at the first frame that reaches the history), from sonar_inharm_track and sonar_inharm only. */
+int sonar_inharm_check(const sonar_inharm_params* p);
+
+/* Everything AnalyzeFrame does after the transform (:236-292, without postProcessResult's tracking), on F
+ * rows of K = W / 2 magnitudes |X[0 .. W/2 - 1]| of the unwindowed frame (:206, :321-328) and each frame's
+ * f0 and its confidence (the analyzer's PitchDetector gives them; here they are inputs).  W = 2 K replaces
+ * params->window_size, K from 4 to 4096: the row is only loaded.  Host pointers, or device pointers for
+ * mag, f0, f0_confidence and every output when device_ptrs is set.  Every output may be NULL and then
+ * costs nothing.  Per frame:
+ *   status: SONAR_INHARM_STATUS_*;
+ *   inharmonicity (raw, before postProcessResult's smoothing), std_dev, confidence;
+ *   f0_out, f0_confidence_out: the inputs (F0Frequency, F0Confidence);
+ *   num_harmonics: len(harmonicData.frequencies); n_deviations: len(HarmonicDeviations), which Statistical's
+ *     outlier removal makes shorter than the other arrays;
+ *   h_number, h_freq, h_ideal, h_amp, h_deviation: F x max(max_harmonics, 0): HarmonicNumbers,
+ *     HarmonicFrequencies, IdealFrequencies, HarmonicAmplitudes, HarmonicDeviations; unused slots are -1 for
+ *     h_number and 0 for the rest;
+ *   estimated_stiffness, model_fit_quality; harmonic_clarity, spectral_purity, partial_coherence;
+ *   r_squared, chi_squared, p_value; quality: SONAR_INHARM_QUALITY_*.
+ * Fields a method leaves unset in Go are 0.  An INVALID_F0 row (f0 <= 0, below min_freq or above max_freq,
+ * :236) has only the two f0 fields and its quality.  An INSUFFICIENT row has the f0 fields and num_harmonics
+ * = the count found; everything else is 0 and quality is -1.  ProcessingTime is always 0 (:1173) and has
+ * no output.  ModelParameters holds values of other outputs: "railsback_coefficient" = inharmonicity and
+ * "fundamental_frequency" = f0_out (Railsback with >= 3 harmonics only), "string_stiffness" =
+ * estimated_stiffness, "string_tension" / "string_length" = the parameters (the String model only).
+ * Quirks of the reference kept here:
+ *  - findHarmonicPeak (:376-416) scans int(max(0, eb - tb)) .. int(min(K - 1, eb + tb)), eb = f W / sr,
+ *    tb = tol f W / sr, with a strict > from maxMag = 0 (an all-zero or empty stretch leaves the start
+ *    bin and a magnitude of 0), then demands a strict local maximum at 1 .. K - 2; the frequency is
+ *    bin sr / W, so the deviation is quantised to bins.  The loop over h stops at the first h f0 > max_freq.
+ *  - Railsback (:467-510, :632-680): 201 values of B from -0.01 by 200 float64 additions of 0.0001 (the last
+ *    is 0.00999999999999999); a grid point whose 1 + B n^2 is negative for some harmonic has a NaN error and
+ *    is skipped; the first strict minimum wins; fewer than 3 harmonics give an empty result.
+ *  - Statistical (:576-610, :735-845): quartiles are gonum's empirical quantile (restated, parity unpinned);
+ *    the chi-squared test needs 5 values, and at 6 or 7 its p-value is 0 or NaN (zero degrees of freedom).
+ *  - The String model overwrites model_fit_quality, Railsback's R^2 included (:874).
+ *  - FletcherMunson's weight above 4 kHz, the clarity, the purity, the String fit and the chi-squared test go
+ *    through log10 / exp: parity at a few ulp there, bit for bit elsewhere.
+ * Errors: those of sonar_inharm_check; method BEAT_PATTERN (it needs the samples), K outside [4, 4096], F < 0, NULL mag, f0 or f0_confidence with
+ * frames due, and (host pointers only) a non-finite f0 -> SONAR_ERR_INVALID: the detector cannot give one on
+ * finite PCM, a documented narrowing.  With device pointers such a frame is an INVALID_F0 row.  F == 0
+ * succeeds and writes nothing. */
+int sonar_inharm_from_spectrum(sonar_ctx* ctx, const double* mag /* F x K */, const double* f0,
+                               const double* f0_confidence, int64_t F, int32_t K, const sonar_inharm_params* params,
+                               int32_t* status, double* inharmonicity, double* std_dev, double* confidence,
+                               double* f0_out, double* f0_confidence_out, int32_t* num_harmonics,
+                               int32_t* n_deviations, int32_t* h_number /* F x max_harmonics */, double* h_freq,
+                               double* h_ideal, double* h_amp, double* h_deviation, double* estimated_stiffness,
+                               double* model_fit_quality, double* harmonic_clarity, double* spectral_purity,
+                               double* partial_coherence, double* r_squared, double* chi_squared, double* p_value,
+                               int32_t* quality, int32_t device_ptrs);
+
+/* AnalyzeFrame without postProcessResult's tracking on the F = sonar_pitch_detect_frames(n, W, hop_size)
+ * whole frames of pcm; the outputs are sonar_inharm_from_spectrum's.
+ *  - With a frame due and window_size != 1024: SONAR_ERR_INVALID "audio frame size (W) doesn't match window
+ *    size (1024)" (pitch_detection.go:226 under :231; F100).  F == 0 succeeds.
+ *  - f0 / f0_confidence are sonar_pitch_detect's pitch / confidence on the same frames with
+ *    sonar_pitch_params_default (YIN, 80-1000 Hz, its history carried from frame to frame whatever
+ *    use_temporal_tracking says, F101), bit for bit.
+ *  - The spectrum is the W-point transform of the raw frame, no window (:321), one block per frame, nothing
+ *    but results in device memory.  The transform is go-dsp's in the reference: parity at tolerance.
+ *  - BEAT_PATTERN (:552-573) still runs the harmonic search (which can be INSUFFICIENT) and sets
+ *    num_harmonics, the String model and the metrics, but no confidence and no harmonic array.  Its
+ *    inharmonicity is 0.001 times the coefficient of variation of the lags of FindPeaks(corr, 0.1, 1.0)
+ *    (common/math.go:265: strict local maxima >= 0.1; the distance of 1.0 never binds), corr being
+ *    NewAutoCorrelation(W).Compute of the raw frame: the bits of sonar_autocorr on it, 2 W - 1 values from lag
+ *    -(W - 1), un-normalised at W = 1024.  The lags run over both signs, so their mean is 0 or negative for a
+ *    correlation that is symmetric in its bits, and the result is then 0 (mean > 0 else 0, :728); fewer than
+ *    two peaks give 0 as well.
+ * Errors: those of sonar_inharm_check; n < 0, hop_size < 1 or NULL pcm with frames due -> SONAR_ERR_INVALID. */
+int sonar_inharm_frames(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t hop_size,
+                        const sonar_inharm_params* params, int32_t* status, double* inharmonicity, double* std_dev,
+                        double* confidence, double* f0, double* f0_confidence, int32_t* num_harmonics,
+                        int32_t* n_deviations, int32_t* h_number, double* h_freq, double* h_ideal, double* h_amp,
+                        double* h_deviation, double* estimated_stiffness, double* model_fit_quality,
+                        double* harmonic_clarity, double* spectral_purity, double* partial_coherence,
+                        double* r_squared, double* chi_squared, double* p_value, int32_t* quality,
+                        int32_t device_ptrs);
+
+/* postProcessResult + updateTemporalTracking (:1007-1101) over F rows in order, from an empty history (a fresh
+ * analyzer, or one after Reset).  Host-only, no context.  Frames whose status is not OK pass through
+ * (inharmonicity = raw, the other three 0) and do not touch the history: the early return of :236 comes
+ * before both.  status NULL means every frame is OK.  With use_temporal_tracking and a non-empty history,
+ * inharmonicity = 0.3 raw + 0.7 last, last being the last smoothed value.  temporal_stability = 1 / (1 +
+ * sqrt(gonum variance) / |mean|) of the history (mean != 0), inharmonicity_trend = the slope of gonum's
+ * stat.LinearRegression over x = 0, 1, ..., f0_stability = 1 / (1 + sqrt(variance) / mean) of the f0 history
+ * (mean > 0): each needs three entries and is computed BEFORE the frame's own value enters the history,
+ * which keeps its last temporal_window entries (0 empties it every frame).  Without use_temporal_tracking
+ * nothing is appended and all three stay 0.  gonum is restated from its published rules, parity unpinned.
+ * temporal_window < 0 with tracking: SONAR_ERR_PANIC at the first OK frame (rows before it are written). */
+int sonar_inharm_track(const sonar_inharm_params* params, int64_t F, const int32_t* status,
+                       const double* raw_inharmonicity, const double* f0, double* inharmonicity,
+                       double* temporal_stability, double* inharmonicity_trend, double* f0_stability);
+
+/* AnalyzeSequence (:1181-1193) over the whole frames of pcm: sonar_inharm_frames, then sonar_inharm_track, in
+ * one call.  inharmonicity is the smoothed one; *frames receives F.  The first INSUFFICIENT frame makes Go
+ * return nil and the error: here SONAR_ERR_INVALID with Go's message "insufficient harmonics found: %d < %d",
+ * *error_frame = that frame (-1 otherwise), and the rows before it are written (Go returns none of them); the rows
+ * from that frame on hold what sonar_inharm_frames gives, untracked (inharmonicity raw, the three tracking outputs 0).
+ * With device_ptrs, pcm and every output array are device pointers. */
+int sonar_inharm(sonar_ctx* ctx, const double* pcm, int64_t n, int32_t hop_size, const sonar_inharm_params* params,
+                 int32_t* status, double* inharmonicity, double* temporal_stability, double* inharmonicity_trend,
+                 double* f0_stability, double* std_dev, double* confidence, double* f0, double* f0_confidence,
+                 int32_t* num_harmonics, int32_t* n_deviations, int32_t* h_number, double* h_freq, double* h_ideal,
+                 double* h_amp, double* h_deviation, double* estimated_stiffness, double* model_fit_quality,
+                 double* harmonic_clarity, double* spectral_purity, double* partial_coherence, double* r_squared,
+                 double* chi_squared, double* p_value, int32_t* quality, int64_t* frames, int64_t* error_frame,
+                 int32_t device_ptrs);
+
+/* GetAverageInharmonicity (:1196-1216): the mean of the inharmonicities whose confidence is above 0.5 (a NaN
+ * is not), 0 without any. */
+double sonar_inharm_average(const double* inharmonicity, const double* confidence, int64_t n);
+/* ClassifyInharmonicity (:1272-1286) as SONAR_INHARM_VERY_LOW .. VERY_HIGH (a NaN is "Very High", the else
+ * branch) and EstimateInstrumentType (:1289-1313) as SONAR_INHARM_INSTRUMENT_*, with Go's strings; NULL for
+ * a value outside the enum. */
+int32_t sonar_inharm_classify(double inharmonicity);
+const char* sonar_inharm_class_name(int32_t cls);
+int32_t sonar_inharm_instrument_type(double inharmonicity, double f0);
+const char* sonar_inharm_instrument_name(int32_t type);
+/* getMethodName / getModelName (:1139-1171) and the AnalysisQuality strings; "Unknown" for a method or model
+ * outside the enum, NULL for a quality outside it. */
+const char* sonar_inharm_method_name(int32_t method);
+const char* sonar_inharm_model_name(int32_t model);
+const char* sonar_inharm_quality_name(int32_t quality);
+
 /* result accessors: rows*cols float64 values, row-major; scalars are 1x1 */
 int sonar_result_get(const sonar_result* res, const char* name, const double** data, int64_t* rows,
                      int64_t* cols);

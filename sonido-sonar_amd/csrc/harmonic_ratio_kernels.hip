@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "harmonic_ratio_kernels.h"
+#include "lds_fft.h"
 #include "wave.h"
 #include "../../include/sonar_gpu.h"
 
@@ -38,36 +39,6 @@ namespace sonar {
 namespace {
 
 constexpr int kNone = 0x7fffffff;
-
-// pitch_kernels.hip's transform (xcorr_kernels.hip's butterfly and level loop), restated: device functions
-// do not link across files
-__device__ __forceinline__ void butterfly(double c, double s, double& er, double& ei, double& odr, double& odi) {
-  const double tr = __dsub_rn(__dmul_rn(c, odr), __dmul_rn(s, odi));
-  const double ti = __dadd_rn(__dmul_rn(c, odi), __dmul_rn(s, odr));
-  const double ar = er, ai = ei;
-  er = __dadd_rn(ar, tr); ei = __dadd_rn(ai, ti);
-  odr = __dsub_rn(ar, tr); odi = __dsub_rn(ai, ti);
-}
-
-__device__ void lds_fft(double* sre, double* sim, int N, int logN, const double2* tw) {
-  for (int s = 1; s <= logN; ++s) {
-    __syncthreads();
-    const int h = 1 << (s - 1);
-    const int stride = N >> s;
-    for (int k = threadIdx.x; k < N / 2; k += 256) {
-      const int i = k & (h - 1);
-      const int p = ((k >> (s - 1)) << s) + i, q = p + h;
-      const double2 w = tw[i * stride];
-      double er = sre[p], ei = sim[p], odr = sre[q], odi = sim[q];
-      butterfly(w.x, w.y, er, ei, odr, odi);
-      sre[p] = er; sim[p] = ei; sre[q] = odr; sim[q] = odi;
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ int log2i(int N) { return 31 - __clz(N); }
-__device__ __forceinline__ int bitrev(int j, int logN) { return (int)(__brev((unsigned)j) >> (32 - logN)); }
 
 // hpcp_kernels.hip's key: larger magnitude <-> larger key; -0.0 and +0.0 share one
 __device__ __forceinline__ uint64_t order_key(double m) {
@@ -196,14 +167,14 @@ __global__ __launch_bounds__(256) void hratio_kernel(const HratioArgs a) {
 
   // ---- computeSpectrum: |X| (:278-283)
   if constexpr (PCM) {
-    const int logN = log2i(W);
+    const int logN = fft_log2i(W);
     const int64_t s = fi * a.hop;
     for (int j = tid; j < W; j += 256) {
-      const int src = bitrev(j, logN);
+      const int src = fft_bitrev(j, logN);
       sre[j] = a.pcm[s + src] * a.win[src];
       sim[j] = 0.0;
     }
-    lds_fft(sre, sim, W, logN, a.tw);
+    lds_fft_256(sre, sim, W, logN, a.tw);
     for (int i = tid; i < K; i += 256) A[i] = sqrt(sre[i] * sre[i] + sim[i] * sim[i]);
   } else {
     for (int i = tid; i < K; i += 256) A[i] = a.mag[fi * K + i];

@@ -893,5 +893,51 @@ HratioRow HratioTracker::step(bool smoothing, int len, double raw) {
   return r;
 }
 
+double gonum_linear_regression(const double* x, const double* y, size_t n) {   // common/math.go:237-262, the slope
+  double sx = 0.0, sy = 0.0;
+  for (size_t i = 0; i < n; i++) { sx += x[i]; sy += y[i]; }
+  const double xu = sx / (double)n, yu = sy / (double)n;
+  double ss = 0.0, xc = 0.0, yc = 0.0;
+  for (size_t i = 0; i < n; i++) {
+    const double xd = x[i] - xu, yd = y[i] - yu;
+    ss += xd * yd; xc += xd; yc += yd;
+  }
+  const double cov = (ss - xc * yc / (double)n) / (double)(n - 1);
+  return cov / gonum_variance(x, n);
+}
+
+InharmRow InharmTracker::step(bool tracking, int window, double raw, double f0) {
+  InharmRow r;
+  r.inharmonicity = raw;
+  if (tracking && !hist.empty()) r.inharmonicity = 0.3 * raw + (1.0 - 0.3) * hist.back();   // :1009-1011, :1023-1032
+  const size_t n = hist.size();
+  if (n >= 3) {
+    double s = 0.0;
+    for (double v : hist) s += v;
+    const double mean = s / (double)n;
+    if (mean != 0) r.stability = 1.0 / (1.0 + std::sqrt(gonum_variance(hist.data(), n)) / std::fabs(mean));   // :1034-1050
+    std::vector<double> x(n);
+    for (size_t i = 0; i < n; i++) x[i] = (double)i;
+    r.trend = gonum_linear_regression(x.data(), hist.data(), n);                              // :1052-1066
+  }
+  if (f0_hist.size() >= 3) {                                                                  // :1068-1084
+    const size_t m = f0_hist.size();
+    double s = 0.0;
+    for (double v : f0_hist) s += v;
+    const double mean = s / (double)m;
+    if (mean > 0) r.f0_stability = 1.0 / (1.0 + std::sqrt(gonum_variance(f0_hist.data(), m)) / mean);
+  }
+  if (tracking) {                                                                             // :1086-1101
+    hist.push_back(r.inharmonicity);
+    f0_hist.push_back(f0);
+    const size_t keep = (size_t)std::max(window, 0);
+    if (hist.size() > keep) {
+      hist.erase(hist.begin(), hist.end() - (std::ptrdiff_t)keep);
+      f0_hist.erase(f0_hist.begin(), f0_hist.end() - (std::ptrdiff_t)keep);
+    }
+  }
+  return r;
+}
+
 }  // namespace host
 }  // namespace sonar

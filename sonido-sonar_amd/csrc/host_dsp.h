@@ -197,5 +197,20 @@ struct HratioTracker {
   HratioRow step(bool smoothing, int len, double raw);
 };
 
+// gonum stat.LinearRegression(x, y, nil, false)'s slope: the covariance over the variance of x, both
+// compensated around stat.Mean's means (sums sequential here: parity unpinned, as gonum_variance); n >= 2
+double gonum_linear_regression(const double* x, const double* y, size_t n);
+
+// InharmonicityAnalyzer's postProcessResult + updateTemporalTracking (inharmonicity.go:1007-1101).  One step per
+// frame that reaches them (AnalyzeFrame returns before both on an invalid f0), in order; a fresh tracker is a
+// fresh analyzer (or one after Reset).  The stability, the trend and the f0 stability are computed before the
+// frame's own values enter the histories, which keep their last `window` entries.  window >= 0 (Go panics at
+// :1098 otherwise; the caller refuses it).
+struct InharmRow { double inharmonicity = 0, stability = 0, trend = 0, f0_stability = 0; };
+struct InharmTracker {
+  std::vector<double> hist, f0_hist;   // inharmonicityHistory, f0History, oldest first
+  InharmRow step(bool tracking, int window, double raw, double f0);
+};
+
 }  // namespace host
 }  // namespace sonar

@@ -1528,3 +1528,200 @@ func ClassifyHarmonicRatio(harmonicRatio float64) string {
 func EstimateVoicingQuality(harmonicRatio float64) float64 {
 	return float64(C.sonar_hratio_voicing_quality(C.double(harmonicRatio)))
 }
+
+// ---- InharmonicityAnalyzer seam (algorithms/tonal/inharmonicity.go): NewInharmonicityAnalyzer,
+// NewInharmonicityAnalyzerWithParams, AnalyzeSequence over the whole frames of one signal,
+// GetAverageInharmonicity, ClassifyInharmonicity and EstimateInstrumentType through sonar_inharm and its
+// host-only companions.  The library returns arrays; this file rebuilds InharmonicityResult.
+
+// InharmonicityMethod carries the reference's values (:17-24), which are SONAR_INHARM_*.
+type InharmonicityMethod int
+
+const (
+	InharmonicityRailsback InharmonicityMethod = iota
+	InharmonicityFletcherMunson
+	InharmonicitySpectralDeviation
+	InharmonicityPartialTracking
+	InharmonicityBeatPattern
+	InharmonicityStatistical
+)
+
+// InharmonicityModel carries the reference's values (:29-34), which are SONAR_INHARM_MODEL_*.
+type InharmonicityModel int
+
+const (
+	ModelString InharmonicityModel = iota
+	ModelPipe
+	ModelMembrane
+	ModelGeneral
+)
+
+// InharmonicityParams = tonal.InharmonicityParams (:37-72).
+type InharmonicityParams struct {
+	Method                                                      InharmonicityMethod
+	Model                                                       InharmonicityModel
+	SampleRate, WindowSize, MaxHarmonics, MinHarmonics          int
+	HarmonicTolerance, MinHarmonicStrength                      float64
+	MinFreq, MaxFreq, FreqResolution                            float64
+	ReferenceHarmonic                                           int
+	WeightByAmplitude, UseLogFrequency                          bool
+	StringTension, StringLength, StringStiffness                float64
+	OutlierThreshold, ConfidenceLevel                           float64
+	UseRobustEstimation, UseTemporalTracking                    bool
+	TemporalWindow                                              int
+}
+
+// InharmonicityResult = tonal.InharmonicityResult (:75-118); ProcessingTime is 0 as in the reference
+// (getCurrentTime is a placeholder).
+type InharmonicityResult struct {
+	Inharmonicity, InharmonicityStdDev, InharmonicityConfidence                float64
+	HarmonicDeviations, HarmonicFrequencies, IdealFrequencies, HarmonicAmplitudes []float64
+	HarmonicNumbers                                                            []int
+	F0Frequency, F0Confidence, F0Stability                                     float64
+	EstimatedStiffness, ModelFitQuality                                        float64
+	ModelParameters                                                            map[string]float64
+	HarmonicClarity, SpectralPurity, PartialCoherence                          float64
+	RSquared, ChiSquared, PValue                                               float64
+	TemporalStability, InharmonicityTrend                                      float64
+	Method, Model                                                              string
+	NumHarmonics                                                               int
+	ProcessingTime                                                             float64
+	AnalysisQuality                                                            string
+}
+
+// InharmonicityAnalyzer holds the parameters; the device work is per call.
+type InharmonicityAnalyzer struct {
+	x      *Context
+	params InharmonicityParams
+}
+
+// NewInharmonicityAnalyzer = tonal.NewInharmonicityAnalyzer (:147-180), through sonar_inharm_params_default:
+// WindowSize 4096 included, with which every frame fails as it does in the reference (DESIGN.md F100).
+func (x *Context) NewInharmonicityAnalyzer(sampleRate int) *InharmonicityAnalyzer {
+	var p C.sonar_inharm_params
+	C.sonar_inharm_params_default(&p, C.int32_t(sampleRate))
+	return &InharmonicityAnalyzer{x: x, params: InharmonicityParams{
+		Method: InharmonicityMethod(p.method), Model: InharmonicityModel(p.model), SampleRate: int(p.sample_rate),
+		WindowSize: int(p.window_size), MaxHarmonics: int(p.max_harmonics), MinHarmonics: int(p.min_harmonics),
+		HarmonicTolerance: float64(p.harmonic_tolerance), MinHarmonicStrength: float64(p.min_harmonic_strength),
+		MinFreq: float64(p.min_freq), MaxFreq: float64(p.max_freq), FreqResolution: float64(p.freq_resolution),
+		ReferenceHarmonic: int(p.reference_harmonic), WeightByAmplitude: p.weight_by_amplitude != 0,
+		UseLogFrequency: p.use_log_frequency != 0, StringTension: float64(p.string_tension),
+		StringLength: float64(p.string_length), StringStiffness: float64(p.string_stiffness),
+		OutlierThreshold: float64(p.outlier_threshold), ConfidenceLevel: float64(p.confidence_level),
+		UseRobustEstimation: p.use_robust_estimation != 0, UseTemporalTracking: p.use_temporal_tracking != 0,
+		TemporalWindow: int(p.temporal_window)}}
+}
+
+// NewInharmonicityAnalyzerWithParams = tonal.NewInharmonicityAnalyzerWithParams (:183-196).
+func (x *Context) NewInharmonicityAnalyzerWithParams(params InharmonicityParams) *InharmonicityAnalyzer {
+	return &InharmonicityAnalyzer{x: x, params: params}
+}
+
+func (ia *InharmonicityAnalyzer) cParams() C.sonar_inharm_params {
+	p := ia.params
+	return C.sonar_inharm_params{method: C.int32_t(p.Method), model: C.int32_t(p.Model), sample_rate: C.int32_t(p.SampleRate),
+		window_size: C.int32_t(p.WindowSize), max_harmonics: C.int32_t(p.MaxHarmonics), min_harmonics: C.int32_t(p.MinHarmonics),
+		harmonic_tolerance: C.double(p.HarmonicTolerance), min_harmonic_strength: C.double(p.MinHarmonicStrength),
+		min_freq: C.double(p.MinFreq), max_freq: C.double(p.MaxFreq), freq_resolution: C.double(p.FreqResolution),
+		reference_harmonic: C.int32_t(p.ReferenceHarmonic), weight_by_amplitude: b2i(p.WeightByAmplitude),
+		use_log_frequency: b2i(p.UseLogFrequency), string_tension: C.double(p.StringTension),
+		string_length: C.double(p.StringLength), string_stiffness: C.double(p.StringStiffness),
+		outlier_threshold: C.double(p.OutlierThreshold), confidence_level: C.double(p.ConfidenceLevel),
+		use_robust_estimation: b2i(p.UseRobustEstimation), use_temporal_tracking: b2i(p.UseTemporalTracking),
+		temporal_window: C.int32_t(p.TemporalWindow)}
+}
+
+// AnalyzeSignal is AnalyzeSequence (:1181-1193) over the whole frames of one signal (WindowSize samples every
+// hopSize) on a fresh analyzer, in one sonar_inharm call.  Where the reference returns nil and an error (a frame
+// with too few harmonics, a window that is not the detector's 1024) so does this, with the reference's message.
+func (ia *InharmonicityAnalyzer) AnalyzeSignal(pcm []float64, hopSize int) ([]InharmonicityResult, error) {
+	p := ia.cParams()
+	F := int(C.sonar_pitch_detect_frames(C.int64_t(len(pcm)), p.window_size, C.int32_t(hopSize)))
+	if F == 0 {
+		if rc := C.sonar_inharm_check(&p); rc != C.SONAR_OK {
+			return nil, fmt.Errorf("inharmonicity: parameters refused (%d)", int(rc))
+		}
+		return []InharmonicityResult{}, nil
+	}
+	mh := ia.params.MaxHarmonics
+	if mh < 0 {
+		mh = 0
+	}
+	cols := make([][]float64, 16)
+	for k := range cols {
+		cols[k] = make([]float64, F)
+	}
+	status, num, ndev, quality := make([]int32, F), make([]int32, F), make([]int32, F), make([]int32, F)
+	hn := make([]int32, F*mh+1)
+	hf, hi, ha, hd := make([]float64, F*mh+1), make([]float64, F*mh+1), make([]float64, F*mh+1), make([]float64, F*mh+1)
+	var frames, bad C.int64_t
+	if rc := C.sonar_inharm(ia.x.c, f64p(pcm), C.int64_t(len(pcm)), C.int32_t(hopSize), &p, i32p(status), f64p(cols[0]),
+		f64p(cols[1]), f64p(cols[2]), f64p(cols[3]), f64p(cols[4]), f64p(cols[5]), f64p(cols[6]), f64p(cols[7]), i32p(num),
+		i32p(ndev), i32p(hn), f64p(hf), f64p(hi), f64p(ha), f64p(hd), f64p(cols[8]), f64p(cols[9]), f64p(cols[10]),
+		f64p(cols[11]), f64p(cols[12]), f64p(cols[13]), f64p(cols[14]), f64p(cols[15]), i32p(quality), &frames, &bad,
+		0); rc != C.SONAR_OK {
+		return nil, ia.x.err(rc)
+	}
+	m, model := ia.params.Method, ia.params.Model
+	out := make([]InharmonicityResult, F)
+	for t := range out {
+		r := &out[t]
+		r.F0Frequency, r.F0Confidence = cols[6][t], cols[7][t]
+		r.AnalysisQuality = C.GoString(C.sonar_inharm_quality_name(C.int32_t(quality[t])))
+		if status[t] != C.SONAR_INHARM_STATUS_OK { // the early return of :236-242: nothing else is set
+			continue
+		}
+		r.Inharmonicity, r.TemporalStability, r.InharmonicityTrend, r.F0Stability = cols[0][t], cols[1][t], cols[2][t], cols[3][t]
+		r.InharmonicityStdDev, r.InharmonicityConfidence = cols[4][t], cols[5][t]
+		r.EstimatedStiffness, r.ModelFitQuality = cols[8][t], cols[9][t]
+		r.HarmonicClarity, r.SpectralPurity, r.PartialCoherence = cols[10][t], cols[11][t], cols[12][t]
+		r.RSquared, r.ChiSquared, r.PValue = cols[13][t], cols[14][t], cols[15][t]
+		r.NumHarmonics = int(num[t])
+		n, nd, o := int(num[t]), int(ndev[t]), t*mh
+		if hn[o] >= 0 && n > 0 && mh > 0 { // the method set the harmonic arrays
+			r.HarmonicFrequencies, r.IdealFrequencies, r.HarmonicAmplitudes = hf[o:o+n:o+n], hi[o:o+n:o+n], ha[o:o+n:o+n]
+			r.HarmonicDeviations = hd[o : o+nd : o+nd]
+			r.HarmonicNumbers = make([]int, n)
+			for s := range r.HarmonicNumbers {
+				r.HarmonicNumbers[s] = int(hn[o+s])
+			}
+			if m == InharmonicityRailsback { // :504-507
+				r.ModelParameters = map[string]float64{"railsback_coefficient": cols[0][t], "fundamental_frequency": r.F0Frequency}
+			}
+		}
+		if model == ModelString { // :876-881
+			if r.ModelParameters == nil {
+				r.ModelParameters = map[string]float64{}
+			}
+			r.ModelParameters["string_stiffness"] = r.EstimatedStiffness
+			r.ModelParameters["string_tension"] = ia.params.StringTension
+			r.ModelParameters["string_length"] = ia.params.StringLength
+		}
+		r.Method = C.GoString(C.sonar_inharm_method_name(C.int32_t(m)))
+		r.Model = C.GoString(C.sonar_inharm_model_name(C.int32_t(model)))
+	}
+	return out, nil
+}
+
+func (ia *InharmonicityAnalyzer) GetParameters() InharmonicityParams       { return ia.params }
+func (ia *InharmonicityAnalyzer) SetParameters(params InharmonicityParams) { ia.params = params }
+
+// GetAverageInharmonicity = InharmonicityAnalyzer.GetAverageInharmonicity (:1196-1216).
+func (ia *InharmonicityAnalyzer) GetAverageInharmonicity(results []InharmonicityResult) float64 {
+	v, c := make([]float64, len(results)), make([]float64, len(results))
+	for i := range results {
+		v[i], c[i] = results[i].Inharmonicity, results[i].InharmonicityConfidence
+	}
+	return float64(C.sonar_inharm_average(f64p(v), f64p(c), C.int64_t(len(v))))
+}
+
+// ClassifyInharmonicity = tonal.ClassifyInharmonicity (:1272-1286).
+func ClassifyInharmonicity(inharmonicity float64) string {
+	return C.GoString(C.sonar_inharm_class_name(C.sonar_inharm_classify(C.double(inharmonicity))))
+}
+
+// EstimateInstrumentType = tonal.EstimateInstrumentType (:1289-1313).
+func EstimateInstrumentType(inharmonicity float64, f0 float64) string {
+	return C.GoString(C.sonar_inharm_instrument_name(C.sonar_inharm_instrument_type(C.double(inharmonicity), C.double(f0))))
+}

@@ -397,6 +397,25 @@ def lib():
     L.sonar_hratio_category_name.restype = C.c_char_p
     L.sonar_hratio_voicing_quality.argtypes = [C.c_double]
     L.sonar_hratio_voicing_quality.restype = C.c_double
+    L.sonar_inharm_params_default.argtypes = [C.POINTER(InharmParams), C.c_int32]
+    L.sonar_inharm_params_default.restype = None
+    L.sonar_inharm_check.argtypes = [C.POINTER(InharmParams)]
+    L.sonar_inharm_from_spectrum.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.POINTER(InharmParams)] + \
+        [_vp] * 22 + [C.c_int32]
+    L.sonar_inharm_frames.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(InharmParams)] + [_vp] * 22 + [C.c_int32]
+    L.sonar_inharm_track.argtypes = [C.POINTER(InharmParams), C.c_int64] + [_vp] * 7
+    L.sonar_inharm.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(InharmParams)] + [_vp] * 25 + \
+        [_i64p, _i64p, C.c_int32]
+    L.sonar_inharm_average.argtypes = [_vp, _vp, C.c_int64]
+    L.sonar_inharm_average.restype = C.c_double
+    L.sonar_inharm_classify.argtypes = [C.c_double]
+    L.sonar_inharm_classify.restype = C.c_int32
+    L.sonar_inharm_instrument_type.argtypes = [C.c_double, C.c_double]
+    L.sonar_inharm_instrument_type.restype = C.c_int32
+    for fn in (L.sonar_inharm_class_name, L.sonar_inharm_instrument_name, L.sonar_inharm_method_name,
+               L.sonar_inharm_model_name, L.sonar_inharm_quality_name):
+        fn.argtypes = [C.c_int32]
+        fn.restype = C.c_char_p
     L.sonar_music_alignment_features.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  C.c_int32, _vp, _vp, C.c_int32]
     L.sonar_dtw.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32, _d, _vp, _vp, _vp, _i64p,
@@ -972,6 +991,118 @@ def _hratio_arrays(F, K, mh, want):
     return out
 
 
+# InharmonicityMethod / InharmonicityModel (SONAR_INHARM_*, inharmonicity.go:17-34), the row statuses and the
+# per-frame outputs in the entries' order
+INHARM_METHODS = {"railsback": 0, "fletcher_munson": 1, "spectral_deviation": 2, "partial_tracking": 3,
+                  "beat_pattern": 4, "statistical": 5}
+INHARM_MODELS = {"string": 0, "pipe": 1, "membrane": 2, "general": 3}
+INHARM_OK, INHARM_INVALID_F0, INHARM_INSUFFICIENT = 0, 1, 2
+INHARM_FRAME_FIELDS = ("status", "inharmonicity", "std_dev", "confidence", "f0", "f0_confidence", "num_harmonics",
+                       "n_deviations", "h_number", "h_freq", "h_ideal", "h_amp", "h_deviation", "estimated_stiffness",
+                       "model_fit_quality", "harmonic_clarity", "spectral_purity", "partial_coherence", "r_squared",
+                       "chi_squared", "p_value", "quality")
+INHARM_TRACK_FIELDS = ("inharmonicity", "temporal_stability", "inharmonicity_trend", "f0_stability")
+INHARM_FIELDS = ("status",) + INHARM_TRACK_FIELDS + INHARM_FRAME_FIELDS[2:]
+INHARM_MAX_HARMONICS = 64
+_INHARM_INT = ("status", "num_harmonics", "n_deviations", "h_number", "quality")
+_INHARM_ROWS = ("h_number", "h_freq", "h_ideal", "h_amp", "h_deviation")
+
+
+class InharmParams(C.Structure):
+    """sonar_inharm_params (InharmonicityParams, inharmonicity.go:37-72, field for field)."""
+    _fields_ = [(n, C.c_int32) for n in ("method", "model", "sample_rate", "window_size", "max_harmonics",
+                                         "min_harmonics")] + \
+               [(n, C.c_double) for n in ("harmonic_tolerance", "min_harmonic_strength", "min_freq", "max_freq",
+                                          "freq_resolution")] + \
+               [(n, C.c_int32) for n in ("reference_harmonic", "weight_by_amplitude", "use_log_frequency")] + \
+               [(n, C.c_double) for n in ("string_tension", "string_length", "string_stiffness", "outlier_threshold",
+                                          "confidence_level")] + \
+               [(n, C.c_int32) for n in ("use_robust_estimation", "use_temporal_tracking", "temporal_window")]
+
+
+def inharm_params_default(sample_rate, **kw):
+    """sonar_inharm_params_default: NewInharmonicityAnalyzer(sample_rate)'s parameters (window 4096 included),
+    then the overrides.  method and model take their names."""
+    p = InharmParams()
+    lib().sonar_inharm_params_default(C.byref(p), int(sample_rate))
+    for k, v in kw.items():
+        if k == "method" and isinstance(v, str):
+            v = INHARM_METHODS[v]
+        if k == "model" and isinstance(v, str):
+            v = INHARM_MODELS[v]
+        if not hasattr(p, k):
+            raise TypeError(f"unknown inharmonicity parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def inharm_check(params):
+    """sonar_inharm_check (host only): SONAR_OK or the code of a parameter set the entries refuse."""
+    return int(lib().sonar_inharm_check(C.byref(params)))
+
+
+def inharm_track(params, raw_inharmonicity, f0, status=None):
+    """sonar_inharm_track (host only): postProcessResult + updateTemporalTracking over rows in order, from an
+    empty history -> dict of INHARM_TRACK_FIELDS.  Rows whose status is not INHARM_OK pass through."""
+    r, f = _f64(raw_inharmonicity), _f64(f0)
+    st = None if status is None else np.ascontiguousarray(status, np.int32)
+    F = len(r)
+    out = {k: np.zeros(F) for k in INHARM_TRACK_FIELDS}
+    rc = lib().sonar_inharm_track(C.byref(params), F, _ptr(st), _ptr(r) if F else None, _ptr(f) if F else None,
+                                  *[_ptr(out[k]) for k in INHARM_TRACK_FIELDS])
+    if rc != OK:
+        raise SonarError(rc, "runtime error: slice bounds out of range [%d:1]" % (1 - params.temporal_window)
+                         if rc == ERR_PANIC else "sonar_inharm_track")
+    return out
+
+
+def inharm_average(inharmonicity, confidence):
+    """sonar_inharm_average (host only): GetAverageInharmonicity."""
+    i, c = _f64(inharmonicity), _f64(confidence)
+    return float(lib().sonar_inharm_average(_ptr(i) if len(i) else None, _ptr(c) if len(c) else None, min(len(i), len(c))))
+
+
+def _inharm_name(fn, code):
+    s = fn(int(code))
+    return None if s is None else s.decode()
+
+
+def inharm_classify(inharmonicity):
+    """sonar_inharm_classify (host only): ClassifyInharmonicity's string."""
+    L = lib()
+    return _inharm_name(L.sonar_inharm_class_name, L.sonar_inharm_classify(float(inharmonicity)))
+
+
+def inharm_instrument_type(inharmonicity, f0):
+    """sonar_inharm_instrument_type (host only): EstimateInstrumentType's string."""
+    L = lib()
+    return _inharm_name(L.sonar_inharm_instrument_name, L.sonar_inharm_instrument_type(float(inharmonicity), float(f0)))
+
+
+def inharm_method_name(method):
+    """getMethodName (:1139-1156)."""
+    return _inharm_name(lib().sonar_inharm_method_name, method)
+
+
+def inharm_model_name(model):
+    """getModelName (:1158-1171)."""
+    return _inharm_name(lib().sonar_inharm_model_name, model)
+
+
+def inharm_quality_name(quality):
+    """AnalysisQuality's string of a SONAR_INHARM_QUALITY_* code; None outside the enum (an INSUFFICIENT row)."""
+    return _inharm_name(lib().sonar_inharm_quality_name, quality)
+
+
+def _inharm_arrays(F, mh, want, fields=INHARM_FRAME_FIELDS):
+    """host arrays of the wanted outputs (None for the others)"""
+    out = {}
+    for k in fields:
+        shape = (F, mh) if k in _INHARM_ROWS else (F,)
+        out[k] = np.zeros(shape, np.int32 if k in _INHARM_INT else np.float64) if (want is None or k in want) else None
+    return out
+
+
 _ONSET_ERRORS = {ERR_UNSUPPORTED: "onsets: parameters the library does not reproduce (include/sonar_gpu.h)",
                  ERR_INVALID: "onsets: invalid argument"}
 
@@ -1391,6 +1522,66 @@ class Context:
         """hratio_from_spectrum on device memory (device_ptrs = 1)."""
         self._check(self._L.sonar_hratio_from_spectrum(self._h, mag_ptr, phase_ptr, int(F), int(K), C.byref(params),
                                                        *[out_ptrs.get(k) for k in HRATIO_FRAME_FIELDS], 1))
+
+    def inharm_from_spectrum(self, mag, f0, f0_confidence, params, want=None):
+        """Everything AnalyzeFrame does after the transform, on rows of W / 2 magnitudes of the unwindowed
+        frame and each frame's f0 and its confidence (sonar_inharm_from_spectrum) -> dict of
+        INHARM_FRAME_FIELDS; `want` names the outputs to compute (all by default), the others are None."""
+        mag = np.atleast_2d(_f64(mag))
+        F, K = mag.shape
+        f0, fc = _f64(f0), _f64(f0_confidence)
+        assert len(f0) == F and len(fc) == F
+        out = _inharm_arrays(F, max(params.max_harmonics, 0), want)
+        self._check(self._L.sonar_inharm_from_spectrum(self._h, _ptr(mag) if F else None, _ptr(f0) if F else None,
+                                                       _ptr(fc) if F else None, F, K, C.byref(params),
+                                                       *[_ptr(out[k]) for k in INHARM_FRAME_FIELDS], 0))
+        return out
+
+    def inharm_frames(self, pcm, hop_size, params, want=None):
+        """AnalyzeFrame without the tracking per whole frame of pcm, every method (sonar_inharm_frames) -> dict
+        of INHARM_FRAME_FIELDS."""
+        pcm = _f64(pcm)
+        F = pitch_detect_frames(len(pcm), params.window_size, hop_size)
+        out = _inharm_arrays(F, max(params.max_harmonics, 0), want)
+        self._check(self._L.sonar_inharm_frames(self._h, _ptr(pcm) if len(pcm) else None, len(pcm), int(hop_size),
+                                                C.byref(params), *[_ptr(out[k]) for k in INHARM_FRAME_FIELDS], 0))
+        return out
+
+    def inharm(self, pcm, hop_size, params, want=None):
+        """AnalyzeSequence over the whole frames of pcm (sonar_inharm): the per-frame pass, then the tracker ->
+        dict of INHARM_FIELDS.  Where Go returns nil and an error (the first frame with too few harmonics) this
+        raises SonarError with Go's message; its `frame` attribute is that frame and `rows` the dict, whose
+        rows before that frame are written."""
+        pcm = _f64(pcm)
+        F = pitch_detect_frames(len(pcm), params.window_size, hop_size)
+        out = _inharm_arrays(F, max(params.max_harmonics, 0), want, INHARM_FIELDS)
+        frames, bad = C.c_int64(), C.c_int64(-1)
+        try:
+            self._check(self._L.sonar_inharm(self._h, _ptr(pcm) if len(pcm) else None, len(pcm), int(hop_size),
+                                             C.byref(params), *[_ptr(out[k]) for k in INHARM_FIELDS], C.byref(frames),
+                                             C.byref(bad), 0))
+        except SonarError as e:
+            e.frame, e.rows = bad.value, out
+            raise
+        assert frames.value == F
+        return out
+
+    def inharm_device(self, entry, pcm_ptr, n, hop_size, params, out_ptrs):
+        """sonar_inharm_frames ("frames") or sonar_inharm ("sequence") on device memory (device_ptrs = 1):
+        out_ptrs maps output names to device addresses (missing: not wanted) -> the frame count."""
+        if entry == "frames":
+            self._check(self._L.sonar_inharm_frames(self._h, pcm_ptr, int(n), int(hop_size), C.byref(params),
+                                                    *[out_ptrs.get(k) for k in INHARM_FRAME_FIELDS], 1))
+            return pitch_detect_frames(int(n), params.window_size, hop_size)
+        frames, bad = C.c_int64(), C.c_int64(-1)
+        self._check(self._L.sonar_inharm(self._h, pcm_ptr, int(n), int(hop_size), C.byref(params),
+                                         *[out_ptrs.get(k) for k in INHARM_FIELDS], C.byref(frames), C.byref(bad), 1))
+        return frames.value
+
+    def inharm_from_spectrum_device(self, mag_ptr, f0_ptr, f0_confidence_ptr, F, K, params, out_ptrs):
+        """inharm_from_spectrum on device memory (device_ptrs = 1)."""
+        self._check(self._L.sonar_inharm_from_spectrum(self._h, mag_ptr, f0_ptr, f0_confidence_ptr, int(F), int(K),
+                                                       C.byref(params), *[out_ptrs.get(k) for k in INHARM_FRAME_FIELDS], 1))
 
     def chroma_stft(self, pcm, n_frames, hop, sample_rate, preprocess=True):
         pcm = _f64(pcm)
